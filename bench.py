@@ -15,7 +15,13 @@ PRODUCT entry point -- `for outputs, dets in MultiPoseDetector.process_stream(ba
 `detector_factory['multi_pose'](cfg)` returns (the replacement of lib/detectors/multi_pose.py:29-60): D = --in-flight (default 2)
 consecutive batches captured into ONE hipGraph; D = 1 is `MultiPoseDetector.process` per batch and rides along as
 `config.one_step_in_flight`.  Per-step input copy and fresh `dets` are inside the timing.  Prints ONE JSON line
-on rank 0 with the contract's keys plus
+on rank 0 with the contract's keys.  A plain run does nothing else: set-up, warm-up, the K timed steps, the line.
+
+    python bench.py --gpus N --steps K --warmup W --dump-outputs DIR
+
+also writes what the last timed step returned (the six head maps, `dets`, and at N > 1 the gathered `dets_gathered`) as
+DIR/<name>.npy, float32; weights and images are seeded, so two builds can be compared output for output.  `--full` adds, after
+the timed region,
 
 * `roofline`: the DOMINANT kernel of the step by time (kernel families timed live, in sequence, with HIP events on the
   launch stream): achieved = MFMA FLOPs the kernel executes per second (for a Winograd family 16/36 of the algorithmic
@@ -62,6 +68,11 @@ def parse_args():
                          "the side stream exactly as at N > 1 -- everything of the multi-GPU path except the xGMI wire")
     ap.add_argument("--gather-check", action="store_true",
                     help="N > 1: after the timed region compare every rank's gathered dets (checksum exchange) and its own shard's slot")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline pass, sustained / one-step-in-flight figures, decode alone, other configurations and "
+                         "the CPU baseline (each can still be left out with its --no-* switch); without it a run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -394,6 +405,25 @@ def feed(batches, n):
         yield batches[i % len(batches)]
 
 
+HEAD_NAMES = ("hm", "wh", "hps", "reg", "hm_hp", "hp_offset")
+DUMP_BUDGET = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """`arrays` (name -> host float32 array, the batch on axis 0) as path/<name>.npy.  Over DUMP_BUDGET bytes in all, every array
+    with more than one image keeps the leading images that fit (a fixed sample: the same images on every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        per_image = sum(a.nbytes // a.shape[0] for a in arrays.values())
+        keep = max(1, DUMP_BUDGET // per_image)
+        arrays = {k: a[:keep] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print("outputs of the last timed step -> %s: %s" % (path, {k: tuple(a.shape) for k, a in arrays.items()}), file=sys.stderr)
+
+
 def timed_stream(det, batches, steps, warmup, depth):
     """`steps` steps through the PRODUCT entry point -- `MultiPoseDetector.process_stream(batches, depth)` (depth 1:
     `MultiPoseDetector.process` per batch) -- host clock around one device synchronisation; every step copies its batch into the
@@ -542,10 +572,14 @@ def main():
         gat.submit(dets)
         return prev
 
+    last = []
+
     def run_steps(n, marks=None):
-        """n steps through MultiPoseDetector.process_stream; one HIP event after every step's hand-over."""
-        for _, dets in det.process_stream(feed(batches, n), depth=D):
+        """n steps through MultiPoseDetector.process_stream; one HIP event after every step's hand-over.  `last` holds what the
+        entry point returned for the last step."""
+        for outputs, dets in det.process_stream(feed(batches, n), depth=D):
             hand_over(dets)
+            last[:] = [outputs, dets]
             if marks is not None:
                 marks.append(torch.cuda.Event(enable_timing=True))
                 marks[-1].record()
@@ -569,6 +603,13 @@ def main():
     if grouped:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything else replays a plan: the six maps are the last step's plan buffers
+        arrays = {n: t.float().cpu().numpy() for n, t in zip(HEAD_NAMES, last[0])}
+        arrays["dets"] = last[1].float().cpu().numpy()
+        if grouped:
+            arrays["dets_gathered"] = out.float().cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     rank_ms = {"min": elapsed / args.steps * 1e3, "max": elapsed / args.steps * 1e3}
     wait_total, wait_max = gat.exposed_wait_ms()
     gather_info = None
@@ -639,7 +680,7 @@ def main():
                                       "HIP events on the launch stream, a joint replay's time divided by its %d steps" % D},
                 "end_to_end_tflops": round(eng.flops_per_image * value / world / 1e12, 2),
                 "activation_mb": round(eng.activation_bytes / 1e6, 1)}
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             line["roofline"] = roofline(eng, args.arch, B, wall_ms=ms_step)
             # DVFS (MI355X_MICROARCH.md: short bursts clock higher): the same steps over >= 1000 more AFTER the timed region
             n_sus = max(1000, args.steps)
@@ -670,9 +711,9 @@ def main():
             dec_bytes = B * (18 * hm.shape[2] * hm.shape[3] * 4 + 28800 + 22400)     # hm + hm_hp maps, gathers, dets
             line["decode"] = {"us_per_batch": round(dec_us, 1), "algorithmic_bytes": dec_bytes,
                               "gbps": round(dec_bytes / dec_us / 1e3, 1), "kernels": "nms_topk_kernel + pose_assign_kernel"}
-        if world == 1 and not args.no_profile and not args.no_other_configs and args.arch == "dla_34":
+        if args.full and world == 1 and not args.no_profile and not args.no_other_configs and args.arch == "dla_34":
             line["other_configs"] = other_configs(dev, depth=max(2, D))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.arch)
         print(json.dumps(line), flush=True)
     if grouped:

@@ -2,7 +2,7 @@
 (/root/reference, build container only).  The reference never travels: only the resulting
 .npz data files (inputs are regenerated from seeds by tests/cases.py) are committed.
 
-    python tests/golden/make_golden.py [decode] [nets] [dcn]
+    python tests/golden/make_golden.py [decode] [nets] [dcn] [checks] [spec]
 """
 import os
 import sys
@@ -54,12 +54,51 @@ def gen_flip():
     print("flip", tuple(hps.shape))
 
 
+def gen_checks():
+    """What the tests once asked the imported reference for, recorded: multi_pose_decode on two seeded 64x64 batches (K = 50) and
+    flip_tensor / flip_lr / flip_lr_off on seeded maps -> reference_checks.npz; the TEST / MODEL settings of the experiment YAMLs
+    the presets mirror -> reference_presets.json."""
+    import json
+    import yaml
+    from models import decode as ref_decode
+    from models.decode import multi_pose_decode
+    from models.utils import flip_lr, flip_lr_off, flip_tensor
+    out = {}
+    for seed in (0, 1):
+        t = {k: torch.from_numpy(v) for k, v in cases.decode_random(100 + seed, B=2, H=64, W=64).items()}
+        with torch.no_grad():
+            out["decode_seed%d" % seed] = multi_pose_decode(t["hm"], t["wh"], t["hps"], t["reg"], t["hm_hp"], t["hp_offset"], K=50).numpy()
+    flip_idx = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]]      # multi_pose.py:27
+    r = np.random.RandomState(4)
+    hp = torch.from_numpy(r.randn(2, 17, 6, 10).astype(np.float32))
+    hps = torch.from_numpy(r.randn(2, 34, 6, 10).astype(np.float32))
+    out.update(flip_tensor=flip_tensor(hp).numpy(), flip_lr=flip_lr(hp, flip_idx).numpy(), flip_lr_off=flip_lr_off(hps, flip_idx).numpy())
+    np.savez_compressed(os.path.join(HERE, "reference_checks.npz"), **out)
+    experiments = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(ref_decode.__file__)))), "experiments")
+    presets = {}
+    for arch, f in (("dla_34", "dla_34_512x512.yaml"), ("res_50", "res_50_512x512.yaml"), ("hrnet", "hrnet_w32_512.yaml"),
+                    ("mobilenetv3", "mobilenetv3_512x512.yaml"), ("shufflenetV2", "shufflenetV2_512x512.yaml")):
+        y = yaml.safe_load(open(os.path.join(experiments, f)))
+        presets[arch] = {"file": "experiments/" + f,
+                         "TEST": {k: y["TEST"][k] for k in ("FLIP_TEST", "NMS", "FIX_RES", "TEST_SCALES", "TOPK") if k in y["TEST"]},
+                         "MODEL": {k: y["MODEL"][k] for k in ("HEAD_CONV", "INTERMEDIATE_CHANNEL")}}
+    with open(os.path.join(HERE, "reference_presets.json"), "w") as fh:
+        json.dump(presets, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("checks", sorted(out), "presets", sorted(presets))
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["decode", "flip", "dcn", "nets"]
     if "decode" in what:
         gen_decode()
     if "flip" in what:
         gen_flip()
+    if "checks" in what:
+        gen_checks()
     if "dcn" in what or "nets" in what:
         import make_golden_nets
         make_golden_nets.main(what)
+    if "spec" in what:
+        import make_golden_nets
+        make_golden_nets.gen_spec()

@@ -93,5 +93,26 @@ def main(what=("nets",)):
         print("nets", arch, [tuple(o.shape) for o in outs][:2], "...")
 
 
+SPEC_ARCHS = ("dla_34", "res_50", "hrnet", "mobilenetv3", "shufflenetV2", "resdcn_18", "resdcn_34", "resdcn_50", "resdcn_101")
+
+
+def gen_spec():
+    """Per network: the reference module's state_dict key names and shapes, and its forward of the seed-5 synthetic checkpoint on
+    a seed-1 64x64 image -> spec_<arch>_64.npz."""
+    from centerpose_amd import synth
+    for arch in SPEC_ARCHS:
+        m = build_reference(arch)
+        ref_sd = m.state_dict()
+        names = sorted(ref_sd)
+        sd = synth.make_state_dict(arch, seed=5)
+        m.load_state_dict(sd, strict=True)
+        with torch.no_grad():
+            outs = m(synth.make_images(1, 64, 64, seed=1))
+        np.savez_compressed(os.path.join(HERE, "spec_%s_64.npz" % arch), keys=np.array(names),
+                            shapes=np.array([",".join(str(d) for d in ref_sd[k].shape) for k in names]),
+                            **{"out%d" % i: o.numpy() for i, o in enumerate(outs)})
+        print("spec", arch, len(names), "keys")
+
+
 if __name__ == "__main__":
     main()

@@ -175,7 +175,7 @@ def test_bench_single_gpu_line_contract():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -222,7 +222,7 @@ def test_bench_single_gpu_line_contract():
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
         with open(os.path.join(ROOT, "gpurun_out", "timed_kernels_dla_34.json"), "w") as f:
-            json.dump({"kernels": sorted(roof["kernels"]), "from": "bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline"}, f, indent=1)
+            json.dump({"kernels": sorted(roof["kernels"]), "from": "bench.py --gpus 1 --full --steps 5 --warmup 2 --no-cpu-baseline"}, f, indent=1)
     except OSError as e:
         print("could not write the timed-kernel list:", e)
     sb = line["other_configs"]["res_50_b8_split_bf16"]

@@ -5,7 +5,7 @@ TAG=${1:-r6}; OUT=gpurun_out/${TAG}final; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -q --timeout 1500 > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log
 grep -E "passed|failed|^FAILED|^ERROR" $OUT/pytest.log | tail -6
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 300 $OUT/bench.err
+timeout 1500 python bench.py --gpus 1 --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 300 $OUT/bench.err
 timeout 600 python bench.py --gpus 1 --force-gather --steps 20 --warmup 5 --no-cpu-baseline --no-profile --gather-check > $OUT/bench_force_gather.json 2> $OUT/bench_force_gather.err; echo "force-gather rc=$?"
 CP_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 8 --batch 2 --steps 5 --warmup 2 --no-cpu-baseline --no-profile --gather-check > $OUT/bench_8rank_rehearsal.json 2> $OUT/bench_8rank_rehearsal.err; echo "8-rank rc=$?"
 python - <<PY
