@@ -35,6 +35,8 @@ class CPlan:
         _lib.check(L.cp_plan_info(self._h, ctypes.byref(B), ctypes.byref(H), ctypes.byref(W), ctypes.byref(no), ctypes.byref(nl)),
                    "cp_plan_info")
         self.B, self.H, self.W, self.n_outputs, self.n_launches = B.value, H.value, W.value, no.value, nl.value
+        # 1: a detections-only plan (outputs 1, 2, 3, 5 hold values only at the peaks of its own decode)
+        self.dets_only = bool(L.cp_plan_dets_only(self._h) == 1)
         self.output_ptrs, self.output_shapes = [], []
         for i in range(self.n_outputs):
             p, shp = ctypes.c_void_p(), (ctypes.c_int * 4)()

@@ -41,12 +41,15 @@ int cp_sizeof_dcn_desc(void);
 int cp_decode_topk_f32(const float*, const float*, int, int, int, int, int, int, float*, int*, void*);
 int cp_decode_assign_f32(const float*, const float*, const float*, const float*, const float*, const int*, int, int, int, int, int, float*,
                          void*);
+int cp_head_points_f32(const float*, int, const int*, const float*, const float*, const float*, const float*, float*, int, int, int, int, int,
+                       int, int, void*);
 }
 
 namespace {
 
 enum { FN_CONV = 1, FN_WINO = 2, FN_DCN = 3, FN_STEM7 = 4, FN_POOL = 5, FN_UPADD = 6, FN_SUMUP = 7, FN_DWCONV = 8, FN_AVGPOOL = 9,
-       FN_SCALEADD = 10, FN_SHUFFLE = 11, FN_HEAD = 12, FN_TOPK = 13, FN_ASSIGN = 14, FN_SPLITK = 15, FN_WINO24G = 16, FN_CONVG = 17, FN_SUMUPG = 18 };   // ops.FN_IDS
+       FN_SCALEADD = 10, FN_SHUFFLE = 11, FN_HEAD = 12, FN_TOPK = 13, FN_ASSIGN = 14, FN_SPLITK = 15, FN_WINO24G = 16, FN_CONVG = 17, FN_SUMUPG = 18,
+       FN_POINTS = 19 };   // ops.FN_IDS
 enum { REF_NULL = 0, REF_BUF = 1, REF_CONST = 2 };
 
 struct Op {
@@ -155,6 +158,9 @@ int run_op(const Op& o, hipStream_t s)
             return cp_decode_topk_f32(P[0], P[1], I[0], I[1], I[2], I[3], I[4], I[5], P[2], reinterpret_cast<int*>(P[3]), s);
         case FN_ASSIGN:
             return cp_decode_assign_f32(P[0], P[1], P[2], P[3], P[4], reinterpret_cast<const int*>(P[5]), I[0], I[1], I[2], I[3], I[4], P[6], s);
+        case FN_POINTS:       // ptrs: feat, ws_inds, w1, b1, w2, b2, out (the four sparse maps); ints: featLd, B, H, W, C, J, K, hc
+            return cp_head_points_f32(P[0], I[0], reinterpret_cast<const int*>(P[1]), P[2], P[3], P[4], P[5], P[6], I[1], I[2], I[3], I[4], I[5],
+                                      I[6], I[7], s);
     }
     cp_set_error("plan: unknown launch function %u", o.fn);
     return 1;
@@ -182,6 +188,7 @@ bool arity_ok(const Op& o)
         case FN_SPLITK: return o.ptrs.size() == 4 && o.ints.size() == 6;
         case FN_TOPK: return o.ptrs.size() == 4 && o.ints.size() == 6;
         case FN_ASSIGN: return o.ptrs.size() == 7 && o.ints.size() == 5;
+        case FN_POINTS: return o.ptrs.size() == 7 && o.ints.size() == 8;
     }
     return false;
 }
@@ -406,6 +413,16 @@ extern "C" int cp_plan_info(const cp_plan* pl, int* B, int* H, int* W, int* n_ou
 
 extern "C" float* cp_plan_input(const cp_plan* pl) { return pl ? pl->input : nullptr; }
 
+// A detections-only plan (Engine(..., dets_only=True)) evaluates wh / hps / reg / hp_offset only at the decoded peaks: the launch that
+// does so is what identifies it (no header field: plan files of every earlier writer keep loading unchanged).
+extern "C" int cp_plan_dets_only(const cp_plan* pl)
+{
+    if (!pl) return -1;
+    for (const Op& o : pl->ops)
+        if (o.fn == FN_POINTS) return 1;
+    return 0;
+}
+
 extern "C" int cp_plan_output(const cp_plan* pl, int i, float** dev_ptr, int shape[4])
 {
     CP_CHECK_ARG(pl && i >= 0 && i < (int)pl->outs.size(), "plan_output: index %d out of range", i);
@@ -475,6 +492,10 @@ extern "C" int cp_plan_process(cp_plan* pl, const float* images, int K, float* d
         if (e != hipSuccess) { cp_set_error("plan_process: copy of the detections failed: %s", hipGetErrorString(e)); return 2; }
         return 0;
     }
+    // outputs 1, 2, 3, 5 of a detections-only plan hold values only at the peaks of its own decode: a decode with another K would read
+    // pixels nobody wrote
+    CP_CHECK_ARG(cp_plan_dets_only(pl) == 0, "plan_process: detections-only plan compiled with decode_k = %d, asked for K = %d",
+                 pl->ops.empty() || pl->ops.back().fn != FN_ASSIGN ? -1 : pl->ops.back().ints[4], K);
     if (pl->ws_K < K) {
         if (pl->ws_scores) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(pl->ws_scores); (void)hipFree(pl->ws_inds); }
         pl->ws_scores = nullptr; pl->ws_inds = nullptr; pl->ws_K = 0;

@@ -208,24 +208,58 @@ class MultiPoseDetector(BaseDetector):
         return (not self.cfg.TEST.FLIP_TEST and loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS
                 and hasattr(self.model, "process"))
 
-    def process_stream(self, batches, depth=2):
+    def _dets_only_refusal(self, return_time=False):
+        """Why `dets_only=True` cannot run here, or None.  The mode exists on the one-replay path only: the flip merge needs the
+        mirrored maps at every pixel, a head gated off by cfg.LOSS changes what the decode reads, and the 'net' / 'dec' timers of
+        `return_time` time a forward and a decode that a detections-only step does not separate."""
+        loss = self.cfg.LOSS
+        if return_time:
+            return "dets_only=True cannot time 'net' / 'dec' separately (return_time=True)"
+        if self.cfg.TEST.FLIP_TEST:
+            return "dets_only=True does not support TEST.FLIP_TEST (the flip merge needs the dense maps)"
+        if not (loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS):
+            return "dets_only=True needs every head enabled by cfg.LOSS (REG_OFFSET, HM_HP, REG_HP_OFFSET, no MSE_LOSS)"
+        if not self._one_replay_path():
+            return "dets_only=True needs a model with the one-replay process()"
+        return None
+
+    def process_stream(self, batches, depth=2, dets_only=False):
+        """See `_stream`.  dets_only=True: detections-only plans (`process`); refused with ValueError where `process` refuses it --
+        checked here, before the first batch is taken."""
+        if dets_only:
+            why = self._dets_only_refusal()
+            if why:
+                raise ValueError(why)
+        return self._stream(batches, depth, dets_only)
+
+    def _stream(self, batches, depth=2, dets_only=False):
         """`process` over an iterable of image batches with `depth` steps in flight (model.BackBoneWithHead.process_many): a
         generator of `(outputs, dets)` per batch, in order, each bit-identical to `process(batch)`.  Two consecutive batches are
         captured into one hipGraph so that one step's kernels fill the other's launch gaps: throughput up, a batch's result
         available only with its group (latency ~ depth x).  Configurations that need host logic between forward and decode
         (FLIP_TEST, a head gated off by cfg.LOSS) run batch by batch through `process`.  The batched-throughput entry point of
         BASELINE.json's metric; the reference has one image at a time (multi_pose.py:29-60, base_detector.py:79-140)."""
+        extra = {"dets_only": True} if dets_only else {}      # the default calls stay exactly what they were
         if self._one_replay_path() and hasattr(self.model, "process_many"):
             # (no torch.no_grad() around the yields: a grad mode entered inside a generator leaks into the consumer between
             # yields; nothing on this path records autograd history anyway -- raw HIP launches and a clone of a plain tensor)
-            for r in self.model.process_many(batches, self.cfg.TEST.TOPK, depth):
+            for r in self.model.process_many(batches, self.cfg.TEST.TOPK, depth, **extra):
                 yield r
             return
         for images in batches:
-            yield self.process(images)
+            yield self.process(images, **extra)
 
-    def process(self, images, return_time=False):
-        """multi_pose.py:29-60.  images: float32 NCHW, mean/std-normalised, on the HIP device."""
+    def process(self, images, return_time=False, dets_only=False):
+        """multi_pose.py:29-60.  images: float32 NCHW, mean/std-normalised, on the HIP device.
+        dets_only=True (opt-in): a detections-only plan -- hm / hm_hp dense, wh / hps / reg / hp_offset evaluated only at the
+        decoded peaks -> ([hm, None, None, None, hm_hp, None], dets).  One-replay path only: FLIP_TEST, a head gated off by
+        cfg.LOSS or return_time=True raise ValueError (there is no silent fall-back to the dense plan)."""
+        if dets_only:
+            why = self._dets_only_refusal(return_time)
+            if why:
+                raise ValueError(why)
+            with torch.no_grad():
+                return self.model.process(images, self.cfg.TEST.TOPK, dets_only=True)
         if not return_time and self._one_replay_path():
             # no stage timing asked for and nothing to do between forward and decode: both in ONE graph replay (the peak
             # extraction overlaps the last head convolutions).  `run()` keeps the two-stage form for its 'net' / 'dec' timers.

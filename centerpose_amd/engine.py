@@ -19,6 +19,7 @@ from .nets import Act
 
 
 DECODE_TOPK = "decode.nms_topk"      # launch name of the peak extraction: the one launch the scheduler prefers (plan_schedule)
+SPARSE_HEADS = ("wh", "hps", "reg", "hp_offset")   # the heads a detections-only plan evaluates at the decoded peaks only
 
 
 def normalize_state_dict(sd, arch=None):
@@ -70,8 +71,12 @@ class BufferPool:
 
 
 class PlanBuilder(nets.Graph):
-    def __init__(self, sd, B, device, sigmoid_heads=True, const_cache=None):
+    def __init__(self, sd, B, device, sigmoid_heads=True, const_cache=None, dets_only=False):
         super().__init__()
+        # detections-only: emit_head computes hm / hm_hp densely and leaves the SPARSE_HEADS to one points launch after the peak
+        # extraction (Engine._add_decode); `points` keeps the head input alive (a reused pool slot would be garbage by then)
+        self.dets_only = dets_only
+        self.points = None
         self.sd, self.B, self.dev = sd, B, device
         # shape-independent constants shared by the plans of one model (uploaded checkpoint tensors, Winograd-domain weights):
         # with FIX_RES = false every new image size compiles a plan, and re-uploading / re-transforming 20 M parameters each time
@@ -449,6 +454,8 @@ class PlanBuilder(nets.Graph):
         head's 1x1 right after its 3x3 on the same (B*H*W*hc*4 B = 268 MB at B=16) buffer keeps the
         intermediate resident in the 256 MiB Infinity Cache instead of streaming 1.6 GB through HBM."""
         H, W = feat.H, feat.W
+        if self.dets_only:
+            self.points = self.head_points_consts(feat, p, hc)
         # (a batch-dependent rule like the block-count ones: evaluated at batch 1 under CP_BATCH_INVARIANT=1, ADVICE r5)
         per_head = ops.rule_batch(self.B) * H * W * hc * 4 <= 300 * (1 << 20) and hc >= 64
         ft = feat.t
@@ -465,6 +472,9 @@ class PlanBuilder(nets.Graph):
             self.add("wino" if u3 is not None else "conv", p + ".*.0", 2 * H * W * 6 * hc * feat.C * 9,
                      ops.conv2d_launch([ft], wp3, sc3, sh3, mid.t, kh=3, kw=3, stride=1, pad=1, cout=6 * hc, act=ops.ACT_RELU, wino=u3))
         for i, (h, n) in enumerate(nets.HEADS):
+            if self.dets_only and h in SPARSE_HEADS:
+                outs.append(None)
+                continue
             o = torch.empty((self.B, n, H, W), dtype=torch.float32, device=self.dev)
             wp = ops.pack_conv_weight(self.w("%s.%s.2.weight" % (p, h)))
             sc, sh = ops.fold_bn(n, None, self.w("%s.%s.2.bias" % (p, h)), self.dev)
@@ -505,6 +515,17 @@ class PlanBuilder(nets.Graph):
             outs.append(o)
         self.outputs = outs
         return outs
+
+    def head_points_consts(self, feat, p, hc):
+        """The SPARSE_HEADS branches as the packed constants of cp_head_points_f32 (same checkpoint tensors as the dense launches):
+        dict(feat, hc, w1, b1, w2, b2)."""
+        if hc % 32 or hc > 512 or feat.t.shape[3] > 512:
+            raise ValueError("dets_only: the points kernel needs head_conv % 32 == 0 and <= 512 (got %d) and <= 512 head input channels" % hc)
+        w1 = torch.cat([ops.pack_head_points_weight(self.expand_in(self.w("%s.%s.0.weight" % (p, h)), [feat])) for h in SPARSE_HEADS])
+        b1 = torch.cat([self.w("%s.%s.0.bias" % (p, h)).float() for h in SPARSE_HEADS]).contiguous()
+        w2 = torch.cat([self.w("%s.%s.2.weight" % (p, h)).reshape(-1, hc).float() for h in SPARSE_HEADS]).contiguous()
+        b2 = torch.cat([self.w("%s.%s.2.bias" % (p, h)).float() for h in SPARSE_HEADS]).contiguous()
+        return dict(feat=feat, hc=hc, w1=w1, b1=b1, w2=w2, b2=b2)
 
 
 def list_schedule(deps, durations, nstreams=2, prefer=None):
@@ -562,7 +583,9 @@ class Engine:
     """Static-shape inference engine for one (arch, batch, H, W)."""
 
     def __init__(self, arch, state_dict, batch, height=512, width=512, device="cuda", head_conv=None,
-                 sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None):
+                 sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None, dets_only=False):
+        if dets_only and not decode_k:
+            raise ValueError("dets_only=True needs decode_k: the sparse heads are evaluated at the peaks of the plan's own decode")
         if not torch.cuda.is_available():
             raise _lib.CenterposeHipError("Engine needs a HIP device; there is no CPU fallback")
         _lib.lib()
@@ -579,11 +602,14 @@ class Engine:
                 raise ValueError("parameter %s has shape %s, expected %s" % (k, tuple(sd[k].shape), shp))
         with torch.cuda.device(self.device):
             self.input = torch.zeros((batch, 3, height, width), dtype=torch.float32, device=self.device)
-            pb = PlanBuilder(sd, batch, self.device, sigmoid_heads, const_cache)
+            pb = PlanBuilder(sd, batch, self.device, sigmoid_heads, const_cache, dets_only=bool(dets_only))
             pb.network(self.arch, Act(height, width, 3, self.input), head_conv)
         self.launches = pb.launches
         self.emission = pb.launches    # the list in the order of the reference's forward(); `launches` may later be re-ordered by the schedule
-        self.outputs = pb.outputs
+        self.outputs = pb.outputs      # what forward() returns: [hm, None, None, None, hm_hp, None] for a detections-only plan
+        self.head_maps = pb.outputs    # the six map storages (a detections-only plan: the sparse ones too; what a plan file lists)
+        self.dets_only = bool(dets_only)
+        self._points = pb.points
         self.flops_per_image = pb.flops
         self.activation_bytes = pb.bytes_alloc
         self.graph = None
@@ -593,6 +619,7 @@ class Engine:
         self.dets, self.decode_k = None, None
         if decode_k:
             self._add_decode(int(decode_k), sigmoid_heads)
+        self._points = None
 
     def _add_decode(self, K, sigmoid_heads):
         """multi_pose_decode (lib/models/decode.py:235-308, called at multi_pose.py:55) as the last two launches of the
@@ -601,12 +628,31 @@ class Engine:
         if sigmoid_heads is not True and set(sigmoid_heads) != {"hm", "hm_hp"}:
             raise ValueError("decode inside the schedule needs the sigmoided hm and hm_hp heads")
         hm, wh, hps, reg, hm_hp, hp_offset = self.outputs
-        B, J = hm.shape[0], hps.shape[1] // 2
+        B, J, H, W = hm.shape[0], hm_hp.shape[1], hm.shape[2], hm.shape[3]
         with torch.cuda.device(self.device):
             ws = torch.zeros((2, B, 1 + J, K), dtype=torch.float32, device=self.device)
             self.dets = torch.zeros((B, K, 5 + 3 * J), dtype=torch.float32, device=self.device)
+            if self.dets_only:
+                # ONE storage for the four sparse maps: the points launch's output, so `dependencies` sees its RAW edge to the assign
+                sparse = torch.zeros((B * H * W * (6 + 2 * J),), dtype=torch.float32, device=self.device)
+                views, off = [], 0
+                for n in (2, 2 * J, 2, 2):
+                    views.append(sparse[off:off + B * n * H * W].view(B, n, H, W))
+                    off += B * n * H * W
+                wh, hps, reg, hp_offset = views
+                self.head_maps = [hm, wh, hps, reg, hm_hp, hp_offset]
+                self.activation_bytes += 4 * sparse.numel()
         topk, assign = ops.decode_launches(hm, wh, hps, reg, hm_hp, hp_offset, K, ws, self.dets)
-        self.launches = self.emission = self.launches + [("decode", DECODE_TOPK, 0, topk), ("decode", "decode.pose_assign", 0, assign)]
+        tail = [("decode", DECODE_TOPK, 0, topk)]
+        if self.dets_only:
+            pt = self._points
+            hc, C = pt["hc"], pt["feat"].C
+            points = ops.head_points_launch(pt["feat"].t, ws[1], pt["w1"], pt["b1"], pt["w2"], pt["b2"], sparse, hc=hc, J=J, K=K)
+            # algorithmic flops per image: 3 branches at K centres + hp_offset at J*K joint peaks
+            flops = K * 2 * (3 * hc * C * 9 + (4 + 2 * J) * hc) + J * K * 2 * (hc * C * 9 + 2 * hc)
+            tail.append(("points", "head_points", flops * B, points))
+        tail.append(("decode", "decode.pose_assign", 0, assign))
+        self.launches = self.emission = self.launches + tail
         self.activation_bytes += 4 * (ws.numel() + self.dets.numel())
         self.decode_k = K
 

@@ -52,8 +52,12 @@ class BackBoneWithHead:
     def eval(self):
         return self
 
-    def engine_for(self, B, H, W, decode_k=None):
+    def engine_for(self, B, H, W, decode_k=None, dets_only=False):
+        """The compiled plan for (B, H, W) [with the decode inside its schedule: decode_k] [detections-only: dets_only, see
+        `process`], cached per that whole key."""
         key = (B, H, W) if decode_k is None else (B, H, W, int(decode_k))
+        if dets_only:
+            key += ("dets_only",)
         eng = self._engines.get(key)
         if eng is not None:
             self._engines.move_to_end(key)
@@ -62,7 +66,7 @@ class BackBoneWithHead:
             self._engines.popitem(last=False)            # drop the least recently used plan before building the next one
         eng = engine.Engine(self.arch, self._sd, B, H, W, device=self.device, head_conv=self.head_conv,
                             sigmoid_heads=("hm",) + (("hm_hp",) if self.sigmoid_hm_hp else ()), use_graph=self.use_graph,
-                            decode_k=decode_k, const_cache=self._const_cache, sched_cache=self._sched_cache)
+                            decode_k=decode_k, const_cache=self._const_cache, sched_cache=self._sched_cache, dets_only=dets_only)
         self._engines[key] = eng
         return eng
 
@@ -76,39 +80,46 @@ class BackBoneWithHead:
 
     __call__ = forward
 
-    def process(self, x, K=100):
+    def process(self, x, K=100, dets_only=False):
         """forward + multi_pose_decode as ONE hipGraph replay (engine built with the decode inside its schedule):
-        -> ([hm, wh, hps, reg, hm_hp, hp_offset], dets [B, K, 56]).  `dets` is a FRESH tensor owned by the caller, like the
+        -> ([hm, wh, hps, reg, hm_hp, hp_offset], dets [B, K, 56]).
+        dets_only=True: a detections-only plan -- hm / hm_hp dense as always (same launches, same bits), the wh / hps / reg
+        branches evaluated only at the K decoded centres and hp_offset only at the J*K joint peaks (cp_head_points_f32), i.e. at
+        the pixels the decode reads; returns ([hm, None, None, None, hm_hp, None], dets) (the reference's None-gating of heads,
+        multi_pose.py:39-41).  `dets` is a FRESH tensor owned by the caller, like the
         reference's (decode.py:305-307 returns a torch.cat result): a stream-ordered copy of the plan's static buffer
         (22.4 KB per image), so collecting dets over several calls or handing them to `dist.DetsGatherer.submit` is safe.
         The six head maps are the plan's static output buffers (3.8 MB per image), overwritten by the next call -- the same
         contract as `forward`."""
         B, _, H, W = x.shape
-        outs, dets = self.engine_for(B, H, W, decode_k=K).process(x)
+        outs, dets = self.engine_for(B, H, W, decode_k=K, dets_only=dets_only).process(x)
         return outs, dets.clone()
 
-    def pipeline_for(self, B, H, W, decode_k=100, depth=2):
+    def pipeline_for(self, B, H, W, decode_k=100, depth=2, dets_only=False):
         """`depth` instances of the (B, H, W) plan -- instance 0 IS `engine_for(B, H, W, decode_k)`, the others have their own
         activations and static buffers and share this model's packed constants -- scheduled together and captured into ONE
         hipGraph (engine.EnginePipeline).  Cached and evicted like a single plan (one entry of the CP_ENGINE_CACHE budget)."""
         if depth < 2:
             raise ValueError("a pipeline holds at least two steps in flight; use engine_for / process for one")
         key = (B, H, W, int(decode_k), "in-flight", int(depth))
+        if dets_only:
+            key += ("dets_only",)
         pipe = self._engines.get(key)
         if pipe is not None:
             self._engines.move_to_end(key)
             return pipe
-        first = self.engine_for(B, H, W, decode_k)
+        first = self.engine_for(B, H, W, decode_k, dets_only=dets_only)
         rest = [engine.Engine(self.arch, self._sd, B, H, W, device=self.device, head_conv=self.head_conv,
                               sigmoid_heads=("hm",) + (("hm_hp",) if self.sigmoid_hm_hp else ()), use_graph=self.use_graph,
-                              decode_k=decode_k, const_cache=self._const_cache, sched_cache=None) for _ in range(depth - 1)]
+                              decode_k=decode_k, const_cache=self._const_cache, sched_cache=None, dets_only=dets_only)
+                for _ in range(depth - 1)]
         pipe = engine.EnginePipeline.from_engines([first] + rest)
         while len(self._engines) >= max(2, self.max_engines):        # (instance 0's own entry was just used: it is the youngest)
             self._engines.popitem(last=False)
         self._engines[key] = pipe
         return pipe
 
-    def process_many(self, batches, K=100, depth=2):
+    def process_many(self, batches, K=100, depth=2, dets_only=False):
         """`process` over a STREAM of batches with `depth` steps in flight: a generator that takes `depth` batches at a time from
         `batches` (any iterable of float32 NCHW device tensors), copies them into the static inputs of `depth` plan instances,
         replays the ONE hipGraph that holds all of them (`pipeline_for`: the kernels of one step fill the launch gaps and chain
@@ -119,7 +130,8 @@ class BackBoneWithHead:
         B=8 at depth 2).  A last group of fewer than `depth` batches, batches whose shape differs inside a group (FIX_RES =
         false) and depth <= 1 run through `process`, one replay each.  No host synchronisation anywhere.
         The reference has no counterpart: it runs one image at a time, synchronously (lib/detectors/base_detector.py:79-140,
-        multi_pose.py:29-60)."""
+        multi_pose.py:29-60).  dets_only: detections-only plans (`process`)."""
+        extra = {"dets_only": True} if dets_only else {}      # the default calls stay exactly what they were
         it = iter(batches)
         while True:
             group = []
@@ -131,13 +143,13 @@ class BackBoneWithHead:
                 return
             if depth > 1 and len(group) == depth and self.use_graph and len({tuple(x.shape) for x in group}) == 1:
                 B, _, H, W = group[0].shape
-                res = self.pipeline_for(B, H, W, K, depth).process_all(group)
+                res = self.pipeline_for(B, H, W, K, depth, **extra).process_all(group)
                 res = [(outs, dets.clone()) for outs, dets in res]
                 for r in res:
                     yield r
             else:
                 for x in group:
-                    yield self.process(x, K)
+                    yield self.process(x, K, **extra)
 
 
 def create_model(arch, head_conv, cfg):

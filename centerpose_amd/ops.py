@@ -117,6 +117,8 @@ def marshal(fn, desc, ptrs, ints):
         return ptrs[:2] + ints + ptrs[2:]
     if fn == "cp_decode_assign_f32":              # ptrs: wh, kps, reg, hp_offset, ws_scores, ws_inds, dets; ints: B, J, H, W, K
         return ptrs[:6] + ints + [ptrs[6]]
+    if fn == "cp_head_points_f32":                # ptrs: feat, ws_inds, w1, b1, w2, b2, out; ints: featLd, B, H, W, C, J, K, hc
+        return [ptrs[0], ints[0]] + ptrs[1:] + ints[1:]
     raise ValueError("unknown launch function %r" % fn)
 
 
@@ -124,7 +126,7 @@ FN_IDS = {"cp_conv2d_f32": 1, "cp_conv3x3_winograd_f32": 2, "cp_dcn_v2_f32": 3, 
           "cp_maxpool2d_nhwc_f32": 5, "cp_dw_deconv_add_nhwc_f32": 6, "cp_sum_up_nhwc_f32": 7, "cp_dwconv2d_nhwc_f32": 8,
           "cp_global_avgpool_nhwc_f32": 9, "cp_scale_add_nhwc_f32": 10, "cp_shuffle_concat_nhwc_f32": 11, "cp_head3x3_1x1_f32": 12,
           "cp_decode_topk_f32": 13, "cp_decode_assign_f32": 14, "cp_splitk_reduce_f32": 15, "cp_conv3x3_winograd24_group_f32": 16, "cp_conv2d_group_f32": 17,
-          "cp_sum_up_group_nhwc_f32": 18}
+          "cp_sum_up_group_nhwc_f32": 18, "cp_head_points_f32": 19}
 
 
 def pad_rows(t, ldw):
@@ -718,3 +720,25 @@ def decode_launches(hm, wh, hps, reg, hm_hp, hp_offset, K, ws, dets):
     topk = Launch("cp_decode_topk_f32", None, [hm, hm_hp, ws[0], ws[1]], [B, cat, J, H, W, K], out_index=2)
     assign = Launch("cp_decode_assign_f32", None, [wh, hps, reg, hp_offset, ws[0], ws[1], dets], [B, J, H, W, K], out_index=6)
     return topk, assign
+
+
+def pack_head_points_weight(w3):
+    """3x3 weights of one head branch over the PHYSICAL input channels [hc, C, 3, 3] -> the k-group order of cp_head_points_f32:
+    [9C/8][2][hc][4], element (kb, h, n, s) = weight of hidden channel n at k = 8 kb + 4 h + s, k = (ky*3 + kx)*C + c."""
+    hc, C = w3.shape[:2]
+    assert C % 16 == 0 and hc % 32 == 0
+    wk = w3.float().permute(2, 3, 1, 0).reshape(9 * C // 8, 2, 4, hc)        # [kb][h][s][n]
+    return wk.permute(0, 1, 3, 2).contiguous().reshape(-1)
+
+
+def head_points_launch(feat, inds, w1, b1, w2, b2, out, *, hc, J, K):
+    """wh / hps / reg at the centre peaks and hp_offset at the joint peaks (cp_head_points_f32) as one launch record.  feat: the head
+    input NHWC [B,H,W,C physical]; inds: the peak extraction's flat indices [B,1+J,K] (the int32 bit patterns in float32, ws[1] of
+    `decode_launches`); w1: the four branches' `pack_head_points_weight` back to back; b1 [4*hc]; w2 [6+2J, hc] and b2 [6+2J]: the
+    1x1 rows of wh, hps, reg, hp_offset; out: ONE storage of B*H*W*(6+2J) floats that holds the four NCHW maps back to back."""
+    B, H, W, C = feat.shape
+    assert tuple(inds.shape) == (B, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == B * H * W * (6 + 2 * J)
+    assert w1.numel() == 4 * 9 * C * hc and b1.numel() == 4 * hc and tuple(w2.shape) == (6 + 2 * J, hc) and b2.numel() == 6 + 2 * J
+    for t in (w1, b1, w2, b2):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    return Launch("cp_head_points_f32", None, [feat, inds, w1, b1, w2, b2, out], [_ld(feat), B, H, W, C, J, K, hc], out_index=6)

@@ -17,7 +17,8 @@ Layout (all integers little-endian; offsets in bytes from the start of the file)
     u32      abi            cp_abi_version() of the library that wrote it (descriptor struct layouts)
     u32      B, H, W        network input [B,3,H,W]
     u32      nbuf, nconst, nops, nout
-    u32      meta_len       JSON (utf-8): {"arch", "flops_per_image", "ops": [{"kind", "name", "flops"}, ...]}
+    u32      meta_len       JSON (utf-8): {"arch", "flops_per_image", "ops": [{"kind", "name", "flops"}, ...]}, plus "dets_only": true
+                            for a detections-only plan (Engine(..., dets_only=True): outputs 1, 2, 3, 5 valid at the decoded peaks only)
     u32      checksum       FNV-1a (32 bit) of every byte behind this 48-byte header (CPPLAN04; 0 in older files).  It catches
                             truncation and bit rot.  A plan file is a TRUSTED artifact like a shared library: readers validate its
                             structure (arity, reference ranges, descriptor sizes), not every extent a kernel derives from it.
@@ -174,7 +175,9 @@ def plan_blob(engine, deterministic=False):
             order, assign, _ = engine.plan_schedule(None)
             launches, streams = [engine.launches[i] for i in order], [assign[i] for i in order]
     meta = {"arch": engine.arch, "flops_per_image": int(engine.flops_per_image)}
-    return serialize(launches, meta, engine.input, engine.outputs, int(_lib.lib().cp_abi_version()), streams)
+    if getattr(engine, "dets_only", False):
+        meta["dets_only"] = True          # outputs 1, 2, 3, 5 hold values at the decoded peaks only (cp_plan_dets_only)
+    return serialize(launches, meta, engine.input, getattr(engine, "head_maps", engine.outputs), int(_lib.lib().cp_abi_version()), streams)
 
 
 def save_plan(engine, path, deterministic=False):
@@ -298,7 +301,10 @@ def load_plan(path, device="cuda", use_graph=True):
         eng.input = view(p["input"]).view(p["B"], 3, p["H"], p["W"])
         eng.input.zero_()
         eng.launches = launches
-        eng.outputs = [view(r).view(*shape) for r, shape in p["outputs"]]
+        eng.head_maps = [view(r).view(*shape) for r, shape in p["outputs"]]
+        eng.dets_only = bool(p["meta"].get("dets_only", False))
+        # a detections-only plan: forward() hands out hm / hm_hp only (the other four maps are valid at the decoded peaks alone)
+        eng.outputs = [None if eng.dets_only and i in (1, 2, 3, 5) else t for i, t in enumerate(eng.head_maps)]
         eng.flops_per_image = p["meta"]["flops_per_image"]
         eng.activation_bytes = 4 * sum(p["buffers"])
         eng.graph = None

@@ -237,6 +237,19 @@ int cp_decode_topk_f32(const float* heat, const float* hm_hp, int B, int cat, in
 int cp_decode_assign_f32(const float* wh, const float* kps, const float* reg, const float* hp_offset, const float* ws_scores,
                          const int* ws_inds, int B, int J, int H, int W, int K, float* dets, void* stream);
 
+/* ---- detections-only heads: wh / hps / reg at the centre peaks, hp_offset at the joint peaks -------------------------------
+ * The four regression branches of the KeypointHead (keypoint.py:14-37: 3x3 conv C -> hc + bias + ReLU -> 1x1 conv hc -> n + bias)
+ * evaluated ONLY at the pixels multi_pose_decode reads of them (decode.py:240-307), between cp_decode_topk_f32 and
+ * cp_decode_assign_f32.  feat: the head input, NHWC [B,H,W,featLd] with C physical channels (C % 16 == 0, 16-B aligned rows);
+ * ws_inds: cp_decode_topk_f32's [B,1+J,K] (row 0: centres, taken % (H*W); rows 1..J: joints).
+ * w1: per branch (wh, hps, reg, hp_offset) [9C/8][2][hc][4], element (kb, h, n, s) = 3x3 weight of hidden channel n at
+ * k = 8kb + 4h + s, k = tap * C + c (tap = ky * 3 + kx); b1: [4][hc]; w2: [6+2J][hc] = the 1x1 rows of wh (2), hps (2J), reg (2),
+ * hp_offset (2); b2: [6+2J].  out: the four NCHW maps [B,n,H,W] back to back in that order (B*H*W*(6+2J) floats).  Writes every
+ * channel of wh / hps / reg at every centre index and both hp_offset channels at every joint index, nothing else; a pixel's
+ * values depend only on its 3x3 patch (duplicates are written with identical bits).  hc % 32 == 0, hc <= 512, C <= 512. */
+int cp_head_points_f32(const float* feat, int featLd, const int* ws_inds, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* out, int B, int H, int W, int C, int J, int K, int hc, void* stream);
+
 /* ---- plan handle: a whole network behind three calls -----------------------------
  * Replaces BackBoneWithHead.forward (lib/models/model.py:57-59: head_model(backbone_model(x))) for one compiled
  * (arch, B, H, W) and, with cp_plan_process, MultiPoseDetector.process (lib/detectors/multi_pose.py:29-60; flip test
@@ -261,6 +274,10 @@ int cp_plan_output(const cp_plan* plan, int i, float** dev_ptr, int shape[4]);
 int cp_plan_forward(cp_plan* plan, const float* images, void* stream);
 int cp_plan_process(cp_plan* plan, const float* images, int K, float* dets, void* stream);
 int cp_plan_destroy(cp_plan* plan);
+/* 1 when the plan was compiled detections-only (Engine(..., decode_k=K, dets_only=True): it holds a cp_head_points_f32 launch),
+ * else 0 (-1: NULL plan).  Such a plan still has six outputs, but outputs 1, 2, 3 and 5 (wh, hps, reg, hp_offset) are valid only at
+ * the peaks the plan's own decode found; cp_plan_process / cp_pipeline_process need K = the plan's decode_k. */
+int cp_plan_dets_only(const cp_plan* plan);
 
 /* ---- steps in flight (round 6): the C-ABI form of MultiPoseDetector.process_stream / engine.EnginePipeline ----------------------
  * Replaces nothing in the reference (it runs one image at a time, synchronously: lib/detectors/base_detector.py:79-140,
