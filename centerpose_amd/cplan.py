@@ -37,6 +37,9 @@ class CPlan:
         self.B, self.H, self.W, self.n_outputs, self.n_launches = B.value, H.value, W.value, no.value, nl.value
         # 1: a detections-only plan (outputs 1, 2, 3, 5 hold values only at the peaks of its own decode)
         self.dets_only = bool(L.cp_plan_dets_only(self._h) == 1)
+        # 1: a flip-test plan (its batch B holds B / 2 image / mirrored-twin pairs; the detections are per pair)
+        self.flip_test = bool(L.cp_plan_flip_test(self._h) == 1)
+        self.dets_batch = self.B // 2 if self.flip_test else self.B
         self.output_ptrs, self.output_shapes = [], []
         for i in range(self.n_outputs):
             p, shp = ctypes.c_void_p(), (ctypes.c_int * 4)()
@@ -60,11 +63,11 @@ class CPlan:
         return [self._copy_out(i) for i in range(self.n_outputs)]
 
     def process(self, images, K=100):
-        """forward + decode in one C call -> dets [B, K, 5 + 3J] (multi_pose.py:29-60 without the flip test)."""
+        """forward + decode in one C call -> dets [B, K, 5 + 3J] (multi_pose.py:29-60; a flip-test plan: [B / 2, K, 5 + 3J])."""
         if tuple(images.shape) != (self.B, 3, self.H, self.W):
             raise ValueError("plan was compiled for input %s, got %s" % ((self.B, 3, self.H, self.W), tuple(images.shape)))
         J = self.output_shapes[4][1]
-        dets = torch.empty((self.B, K, 5 + 3 * J), dtype=torch.float32, device="cuda")
+        dets = torch.empty((self.dets_batch, K, 5 + 3 * J), dtype=torch.float32, device="cuda")
         _lib.check(self._L.cp_plan_process(self._h, _lib.ptr(_lib.f32(images)), int(K), _lib.ptr(dets), _lib.stream()), "cp_plan_process")
         return dets
 
@@ -106,7 +109,7 @@ class CPipeline:
                 raise ValueError("plan was compiled for input %s, got %s" % ((p0.B, 3, p0.H, p0.W), tuple(x.shape)))
         J = p0.output_shapes[4][1]
         imgs = [_lib.f32(x) for x in images]
-        dets = [torch.empty((p0.B, K, 5 + 3 * J), dtype=torch.float32, device="cuda") for _ in range(self.depth)]
+        dets = [torch.empty((p0.dets_batch, K, 5 + 3 * J), dtype=torch.float32, device="cuda") for _ in range(self.depth)]
         ia = (ctypes.c_void_p * self.depth)(*[x.data_ptr() for x in imgs])
         da = (ctypes.c_void_p * self.depth)(*[d.data_ptr() for d in dets])
         _lib.check(self._L.cp_pipeline_process(self._h, ia, int(K), da, _lib.stream()), "cp_pipeline_process")

@@ -43,13 +43,14 @@ int cp_decode_assign_f32(const float*, const float*, const float*, const float*,
                          void*);
 int cp_head_points_f32(const float*, int, const int*, const float*, const float*, const float*, const float*, float*, int, int, int, int, int,
                        int, int, void*);
+int cp_flip_merge_pairs_f32(int, const float* const*, float* const*, const int*, int, int, int, int, const int*, void*);
 }
 
 namespace {
 
 enum { FN_CONV = 1, FN_WINO = 2, FN_DCN = 3, FN_STEM7 = 4, FN_POOL = 5, FN_UPADD = 6, FN_SUMUP = 7, FN_DWCONV = 8, FN_AVGPOOL = 9,
        FN_SCALEADD = 10, FN_SHUFFLE = 11, FN_HEAD = 12, FN_TOPK = 13, FN_ASSIGN = 14, FN_SPLITK = 15, FN_WINO24G = 16, FN_CONVG = 17, FN_SUMUPG = 18,
-       FN_POINTS = 19 };   // ops.FN_IDS
+       FN_POINTS = 19, FN_FLIPPAIRS = 20 };   // ops.FN_IDS
 enum { REF_NULL = 0, REF_BUF = 1, REF_CONST = 2 };
 
 struct Op {
@@ -161,6 +162,9 @@ int run_op(const Op& o, hipStream_t s)
         case FN_POINTS:       // ptrs: feat, ws_inds, w1, b1, w2, b2, out (the four sparse maps); ints: featLd, B, H, W, C, J, K, hc
             return cp_head_points_f32(P[0], I[0], reinterpret_cast<const int*>(P[1]), P[2], P[3], P[4], P[5], P[6], I[1], I[2], I[3], I[4], I[5],
                                       I[6], I[7], s);
+        case FN_FLIPPAIRS:    // ptrs: in x4, out x4, perm, (the storage all outputs live in); ints: n, N, H, W, J, (C, mode) x4
+            return cp_flip_merge_pairs_f32(I[0], reinterpret_cast<const float* const*>(P.data()), reinterpret_cast<float* const*>(P.data() + 4), I + 5,
+                                           I[1], I[2], I[3], I[4], reinterpret_cast<const int*>(P[8]), s);
     }
     cp_set_error("plan: unknown launch function %u", o.fn);
     return 1;
@@ -189,6 +193,7 @@ bool arity_ok(const Op& o)
         case FN_TOPK: return o.ptrs.size() == 4 && o.ints.size() == 6;
         case FN_ASSIGN: return o.ptrs.size() == 7 && o.ints.size() == 5;
         case FN_POINTS: return o.ptrs.size() == 7 && o.ints.size() == 8;
+        case FN_FLIPPAIRS: return o.ptrs.size() == 10 && o.ints.size() == 13 && o.ints[0] >= 1 && o.ints[0] <= 4;
     }
     return false;
 }
@@ -423,6 +428,23 @@ extern "C" int cp_plan_dets_only(const cp_plan* pl)
     return 0;
 }
 
+// A flip-test plan (Engine(..., flip_test=True)) takes N image / mirrored-twin pairs as a batch of 2N and decodes the N merged maps: the
+// merge launch is what identifies it (no header field, as for cp_plan_dets_only).
+extern "C" int cp_plan_flip_test(const cp_plan* pl)
+{
+    if (!pl) return -1;
+    for (const Op& o : pl->ops)
+        if (o.fn == FN_FLIPPAIRS) return 1;
+    return 0;
+}
+
+// Rows of the detections a plan with the decode inside its schedule writes: the assign launch's own batch (ints: B, J, H, W, K) -- the
+// network batch for every plan except a flip-test one, whose decode runs on the N = B / 2 merged pairs.
+static size_t assign_dets_floats(const Op& assign)
+{
+    return (size_t)assign.ints[0] * assign.ints[4] * (5 + 3 * assign.ints[1]);
+}
+
 extern "C" int cp_plan_output(const cp_plan* pl, int i, float** dev_ptr, int shape[4])
 {
     CP_CHECK_ARG(pl && i >= 0 && i < (int)pl->outs.size(), "plan_output: index %d out of range", i);
@@ -488,13 +510,16 @@ extern "C" int cp_plan_process(cp_plan* pl, const float* images, int K, float* d
     // a plan compiled with the decode inside its schedule (Engine(decode_k = K): the peak extraction overlaps the last head
     // convolutions, the whole step is one graph launch): its detections only need to be handed over
     if (!pl->ops.empty() && pl->ops.back().fn == FN_ASSIGN && pl->ops.back().ints[4] == K) {
-        hipError_t e = hipMemcpyAsync(dets, pl->ops.back().ptrs[6], (size_t)B * K * (5 + 3 * J) * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        hipError_t e = hipMemcpyAsync(dets, pl->ops.back().ptrs[6], assign_dets_floats(pl->ops.back()) * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
         if (e != hipSuccess) { cp_set_error("plan_process: copy of the detections failed: %s", hipGetErrorString(e)); return 2; }
         return 0;
     }
     // outputs 1, 2, 3, 5 of a detections-only plan hold values only at the peaks of its own decode: a decode with another K would read
     // pixels nobody wrote
     CP_CHECK_ARG(cp_plan_dets_only(pl) == 0, "plan_process: detections-only plan compiled with decode_k = %d, asked for K = %d",
+                 pl->ops.empty() || pl->ops.back().fn != FN_ASSIGN ? -1 : pl->ops.back().ints[4], K);
+    // a flip-test plan's six outputs are the un-merged maps of the 2N images: a decode of them would not be the flip test
+    CP_CHECK_ARG(cp_plan_flip_test(pl) == 0, "plan_process: flip-test plan compiled with decode_k = %d, asked for K = %d",
                  pl->ops.empty() || pl->ops.back().fn != FN_ASSIGN ? -1 : pl->ops.back().ints[4], K);
     if (pl->ws_K < K) {
         if (pl->ws_scores) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(pl->ws_scores); (void)hipFree(pl->ws_inds); }
@@ -640,8 +665,7 @@ extern "C" int cp_pipeline_process(cp_pipeline* pp, const float* const* images, 
     }
     for (size_t k = 0; k < D; ++k) {
         const cp_plan* pl = pp->plans[k];
-        const int B = pl->outs[0].shape[0], J = pl->outs[4].shape[1];
-        hipError_t e = hipMemcpyAsync(dets[k], pl->ops.back().ptrs[6], (size_t)B * K * (5 + 3 * J) * 4, hipMemcpyDeviceToDevice, s);
+        hipError_t e = hipMemcpyAsync(dets[k], pl->ops.back().ptrs[6], assign_dets_floats(pl->ops.back()) * 4, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) { cp_set_error("pipeline_process: copy of the detections failed: %s", hipGetErrorString(e)); return 2; }
     }
     return 0;

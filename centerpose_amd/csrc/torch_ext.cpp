@@ -208,7 +208,8 @@ at::Tensor plan_process(int64_t handle, const at::Tensor& images, int K)
     check_plan_input(p, images);
     float* ptr; int shp[4];
     CP_CALL(cp_plan_output(p, 4, &ptr, shp), "cp_plan_output");                   // hm_hp: J planes
-    at::Tensor dets = at::empty({images.size(0), K, 5 + 3 * shp[1]}, images.options());
+    const int64_t rows = cp_plan_flip_test(p) == 1 ? images.size(0) / 2 : images.size(0);      // a flip-test plan: one row block per pair
+    at::Tensor dets = at::empty({rows, K, 5 + 3 * shp[1]}, images.options());
     CP_CALL(cp_plan_process(p, images.data_ptr<float>(), K, dets.data_ptr<float>(), cur_stream(images)), "cp_plan_process");
     return dets;
 }
@@ -249,10 +250,11 @@ std::vector<at::Tensor> pipeline_process(int64_t handle, const std::vector<at::T
     std::vector<at::Tensor> dets;
     float* ptr; int shp[4];
     CP_CALL(cp_plan_output(box->plans[0], 4, &ptr, shp), "cp_plan_output");       // hm_hp: J planes
+    const bool flip = cp_plan_flip_test(box->plans[0]) == 1;                         // per pair, not per image
     for (const at::Tensor& x : images) {
         check_plan_input(box->plans[0], x);
         in.push_back(x.data_ptr<float>());
-        dets.push_back(at::empty({x.size(0), K, 5 + 3 * shp[1]}, x.options()));
+        dets.push_back(at::empty({flip ? x.size(0) / 2 : x.size(0), K, 5 + 3 * shp[1]}, x.options()));
         out.push_back(dets.back().data_ptr<float>());
     }
     CP_CALL(cp_pipeline_process(box->pipe, in.data(), K, out.data(), cur_stream(images[0])), "cp_pipeline_process");

@@ -208,6 +208,13 @@ class MultiPoseDetector(BaseDetector):
         return (not self.cfg.TEST.FLIP_TEST and loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS
                 and hasattr(self.model, "process"))
 
+    def _flip_replay_path(self):
+        """The flip test as ONE graph replay (model.process(..., flip_test=True)): FLIP_TEST on, every head enabled by cfg.LOSS (the
+        plan merges and decodes all six), a model with the one-replay process().  `return_time` keeps the two-stage path."""
+        loss = self.cfg.LOSS
+        return (self.cfg.TEST.FLIP_TEST and loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS
+                and hasattr(self.model, "process"))
+
     def _dets_only_refusal(self, return_time=False):
         """Why `dets_only=True` cannot run here, or None.  The mode exists on the one-replay path only: the flip merge needs the
         mirrored maps at every pixel, a head gated off by cfg.LOSS changes what the decode reads, and the 'net' / 'dec' timers of
@@ -251,6 +258,9 @@ class MultiPoseDetector(BaseDetector):
 
     def process(self, images, return_time=False, dets_only=False):
         """multi_pose.py:29-60.  images: float32 NCHW, mean/std-normalised, on the HIP device.
+        FLIP_TEST: images are image / mirrored-twin pairs, image n at batch 2n and its twin at 2n + 1 (torch.cat of pre_process
+        outputs) -> (the six un-merged maps, dets [B / 2, K, 56]) in one replay; return_time=True and heads gated off by cfg.LOSS keep
+        the two-stage path with a batch of exactly 2.
         dets_only=True (opt-in): a detections-only plan -- hm / hm_hp dense, wh / hps / reg / hp_offset evaluated only at the
         decoded peaks -> ([hm, None, None, None, hm_hp, None], dets).  One-replay path only: FLIP_TEST, a head gated off by
         cfg.LOSS or return_time=True raise ValueError (there is no silent fall-back to the dense plan)."""
@@ -260,6 +270,14 @@ class MultiPoseDetector(BaseDetector):
                 raise ValueError(why)
             with torch.no_grad():
                 return self.model.process(images, self.cfg.TEST.TOPK, dets_only=True)
+        if not return_time and self._flip_replay_path():
+            # the flip test for N = B / 2 image / mirrored-twin pairs in ONE replay: the merge and the decode of the merged maps are
+            # inside the plan's schedule.  outputs: the six un-merged [B] maps (static buffers); dets: fresh, [N, K, 56].
+            B = images.shape[0]
+            if B < 2 or B % 2:
+                raise ValueError("FLIP_TEST needs image / mirrored-twin pairs: an even batch [img0, twin0, img1, twin1, ...], got %d" % B)
+            with torch.no_grad():
+                return self.model.process(images, self.cfg.TEST.TOPK, flip_test=True)
         if not return_time and self._one_replay_path():
             # no stage timing asked for and nothing to do between forward and decode: both in ONE graph replay (the peak
             # extraction overlaps the last head convolutions).  `run()` keeps the two-stage form for its 'net' / 'dec' timers.

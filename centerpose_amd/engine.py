@@ -20,6 +20,8 @@ from .nets import Act
 
 DECODE_TOPK = "decode.nms_topk"      # launch name of the peak extraction: the one launch the scheduler prefers (plan_schedule)
 SPARSE_HEADS = ("wh", "hps", "reg", "hp_offset")   # the heads a detections-only plan evaluates at the decoded peaks only
+FLIP_PEAKS = "flip.merge_peaks"      # flip-test plans: the merge of hm / hm_hp, preferred by the scheduler like the peak extraction
+FLIP_IDX = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))     # left / right joint pairs (multi_pose.py:27)
 
 
 def normalize_state_dict(sd, arch=None):
@@ -583,9 +585,18 @@ class Engine:
     """Static-shape inference engine for one (arch, batch, H, W)."""
 
     def __init__(self, arch, state_dict, batch, height=512, width=512, device="cuda", head_conv=None,
-                 sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None, dets_only=False):
+                 sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None, dets_only=False,
+                 flip_test=False):
         if dets_only and not decode_k:
             raise ValueError("dets_only=True needs decode_k: the sparse heads are evaluated at the peaks of the plan's own decode")
+        if flip_test:
+            if batch % 2:
+                raise ValueError("flip_test=True needs image / mirrored-twin pairs: an even batch [img0, twin0, img1, twin1, ...], got %d"
+                                 % batch)
+            if not decode_k:
+                raise ValueError("flip_test=True needs decode_k: the merged maps exist only inside the plan, for its own decode")
+            if dets_only:
+                raise ValueError("flip_test=True does not combine with dets_only=True (the flip merge needs the dense maps)")
         if not torch.cuda.is_available():
             raise _lib.CenterposeHipError("Engine needs a HIP device; there is no CPU fallback")
         _lib.lib()
@@ -609,6 +620,7 @@ class Engine:
         self.outputs = pb.outputs      # what forward() returns: [hm, None, None, None, hm_hp, None] for a detections-only plan
         self.head_maps = pb.outputs    # the six map storages (a detections-only plan: the sparse ones too; what a plan file lists)
         self.dets_only = bool(dets_only)
+        self.flip_test = bool(flip_test)
         self._points = pb.points
         self.flops_per_image = pb.flops
         self.activation_bytes = pb.bytes_alloc
@@ -629,6 +641,12 @@ class Engine:
             raise ValueError("decode inside the schedule needs the sigmoided hm and hm_hp heads")
         hm, wh, hps, reg, hm_hp, hp_offset = self.outputs
         B, J, H, W = hm.shape[0], hm_hp.shape[1], hm.shape[2], hm.shape[3]
+        merges = []
+        if self.flip_test:
+            # multi_pose.py:45-53 for N = B / 2 pairs inside the schedule: two merge launches, each into ONE storage, and the decode
+            # of the N merged maps.  The peak merge (hm, hm_hp) feeds the peak extraction and may run beside the remaining heads.
+            hm, wh, hps, reg, hm_hp, hp_offset, merges = self._flip_merges(J)
+            B = B // 2
         with torch.cuda.device(self.device):
             ws = torch.zeros((2, B, 1 + J, K), dtype=torch.float32, device=self.device)
             self.dets = torch.zeros((B, K, 5 + 3 * J), dtype=torch.float32, device=self.device)
@@ -643,7 +661,7 @@ class Engine:
                 self.head_maps = [hm, wh, hps, reg, hm_hp, hp_offset]
                 self.activation_bytes += 4 * sparse.numel()
         topk, assign = ops.decode_launches(hm, wh, hps, reg, hm_hp, hp_offset, K, ws, self.dets)
-        tail = [("decode", DECODE_TOPK, 0, topk)]
+        tail = merges[:1] + [("decode", DECODE_TOPK, 0, topk)] + merges[1:]
         if self.dets_only:
             pt = self._points
             hc, C = pt["hc"], pt["feat"].C
@@ -655,6 +673,34 @@ class Engine:
         self.launches = self.emission = self.launches + tail
         self.activation_bytes += 4 * (ws.numel() + self.dets.numel())
         self.decode_k = K
+
+    def _flip_merges(self, J):
+        """The merged maps of a flip-test plan and their two launches: -> (hm, wh, hps, reg, hm_hp, hp_offset as [N] views, launches)."""
+        if J != 17:
+            raise ValueError("flip_test=True swaps the 17 COCO joints (FLIP_IDX); this plan has %d" % J)
+        perm = list(range(J))
+        for a, b in FLIP_IDX:
+            perm[a], perm[b] = b, a
+        modes = ops.FLIP_MODES
+        groups = (((0, modes["flip"]), (4, modes["joints"])),
+                  ((1, modes["flip"]), (2, modes["offsets"]), (3, modes["copy"]), (5, modes["copy"])))
+        merged = [None] * 6
+        launches = []
+        with torch.cuda.device(self.device):
+            permt = torch.tensor(perm, dtype=torch.int32, device=self.device).view(torch.float32)
+            for gi, group in enumerate(groups):
+                srcs = [self.outputs[i] for i, _ in group]
+                N, H, W = srcs[0].shape[0] // 2, srcs[0].shape[2], srcs[0].shape[3]
+                whole = torch.zeros((sum(N * s.shape[1] * H * W for s in srcs),), dtype=torch.float32, device=self.device)
+                maps, off = [], 0
+                for (i, mode), s in zip(group, srcs):
+                    n = N * s.shape[1] * H * W
+                    merged[i] = whole[off:off + n].view(N, s.shape[1], H, W)
+                    maps.append((s, merged[i], mode))
+                    off += n
+                self.activation_bytes += 4 * whole.numel()
+                launches.append(("flip", FLIP_PEAKS if gi == 0 else "flip.merge_regress", 0, ops.flip_pairs_launch(maps, whole, permt)))
+        return tuple(merged) + (launches,)
 
     def process(self, images):
         """forward + decode in one replay (engines built with `decode_k`): -> (the six heads, dets [B, K, 5+3J]); static
@@ -738,7 +784,7 @@ class Engine:
         # the peak extraction (288 small blocks, no MFMA) needs hm / hm_hp only: as soon as those two heads are done it goes beside the
         # remaining head convolutions instead of behind them (a 56 us tail of the step at B = 16 otherwise)
         ll = self.launches if launches is None else launches
-        prefer = [kind == "decode" and name == DECODE_TOPK for (kind, name, _, _) in ll] if os.environ.get("CP_SCHED_PREFER", "1") != "0" else None
+        prefer = [(kind, name) in (("decode", DECODE_TOPK), ("flip", FLIP_PEAKS)) for (kind, name, _, _) in ll] if os.environ.get("CP_SCHED_PREFER", "1") != "0" else None
         return list_schedule(self.dependencies(launches), durations, nstreams, prefer)
 
     def _run_branches(self, main, nstreams, deps, assign=None):
@@ -876,7 +922,7 @@ class Engine:
         """Algorithmic (compulsory) HBM bytes of every launch: each tensor argument once -- inputs, residual, the weights
         the kernel actually reads (Winograd launches carry U, not the direct weights), output."""
         # (a grouped launch lists every member's output AND the storage they all live in: the latter is not counted again)
-        grouped = ("cp_conv3x3_winograd24_group_f32", "cp_conv2d_group_f32", "cp_sum_up_group_nhwc_f32")
+        grouped = ("cp_conv3x3_winograd24_group_f32", "cp_conv2d_group_f32", "cp_sum_up_group_nhwc_f32", "cp_flip_merge_pairs_f32")
         return [sum(4 * t.numel() for t in (launch.tensors[:-1] if launch.fn in grouped else launch.tensors) if t is not None)
                 for _, _, _, launch in (self.launches if launches is None else launches)]
 

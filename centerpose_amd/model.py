@@ -52,12 +52,16 @@ class BackBoneWithHead:
     def eval(self):
         return self
 
-    def engine_for(self, B, H, W, decode_k=None, dets_only=False):
+    def engine_for(self, B, H, W, decode_k=None, dets_only=False, flip_test=False):
         """The compiled plan for (B, H, W) [with the decode inside its schedule: decode_k] [detections-only: dets_only, see
-        `process`], cached per that whole key."""
+        `process`] [B / 2 image / mirrored-twin pairs merged inside the plan: flip_test], cached per that whole key."""
         key = (B, H, W) if decode_k is None else (B, H, W, int(decode_k))
         if dets_only:
             key += ("dets_only",)
+        extra = {}
+        if flip_test:
+            key += ("flip",)
+            extra["flip_test"] = True
         eng = self._engines.get(key)
         if eng is not None:
             self._engines.move_to_end(key)
@@ -66,8 +70,13 @@ class BackBoneWithHead:
             self._engines.popitem(last=False)            # drop the least recently used plan before building the next one
         eng = engine.Engine(self.arch, self._sd, B, H, W, device=self.device, head_conv=self.head_conv,
                             sigmoid_heads=("hm",) + (("hm_hp",) if self.sigmoid_hm_hp else ()), use_graph=self.use_graph,
-                            decode_k=decode_k, const_cache=self._const_cache, sched_cache=self._sched_cache, dets_only=dets_only)
+                            decode_k=decode_k, const_cache=self._const_cache, sched_cache=self._sched_cache, dets_only=dets_only,
+                            **extra)
         self._engines[key] = eng
+        if flip_test:
+            # a flip-test plan holds the whole forward-only plan of its shape (same six maps, same bits) plus the merge and decode:
+            # it replaces that plan in the cache, and `forward` at this shape replays it (one plan per shape, as before)
+            self._engines.pop((B, H, W), None)
         return eng
 
     def forward(self, x):
@@ -76,23 +85,32 @@ class BackBoneWithHead:
         in-place sigmoid of MultiPoseDetector.process (multi_pose.py:35-37) is fused into the
         head epilogue."""
         B, _, H, W = x.shape
+        if (B, H, W) not in self._engines:
+            flip = next((k for k in self._engines if k[:3] == (B, H, W) and k[-1] == "flip"), None)
+            if flip is not None:                     # engine_for(..., flip_test=True) replaced the forward-only plan of this shape
+                self._engines.move_to_end(flip)
+                return self._engines[flip](x)
         return self.engine_for(B, H, W)(x)
 
     __call__ = forward
 
-    def process(self, x, K=100, dets_only=False):
+    def process(self, x, K=100, dets_only=False, flip_test=False):
         """forward + multi_pose_decode as ONE hipGraph replay (engine built with the decode inside its schedule):
         -> ([hm, wh, hps, reg, hm_hp, hp_offset], dets [B, K, 56]).
         dets_only=True: a detections-only plan -- hm / hm_hp dense as always (same launches, same bits), the wh / hps / reg
         branches evaluated only at the K decoded centres and hp_offset only at the J*K joint peaks (cp_head_points_f32), i.e. at
         the pixels the decode reads; returns ([hm, None, None, None, hm_hp, None], dets) (the reference's None-gating of heads,
-        multi_pose.py:39-41).  `dets` is a FRESH tensor owned by the caller, like the
+        multi_pose.py:39-41).
+        flip_test=True: x holds N = B / 2 image / mirrored-twin pairs (image n at 2n, its twin at 2n + 1); the flip merge
+        (multi_pose.py:45-53) and the decode of the N merged pairs run inside the same replay -> (the six un-merged [B] maps, as the
+        reference returns them, dets [N, K, 56]).  `dets` is a FRESH tensor owned by the caller, like the
         reference's (decode.py:305-307 returns a torch.cat result): a stream-ordered copy of the plan's static buffer
         (22.4 KB per image), so collecting dets over several calls or handing them to `dist.DetsGatherer.submit` is safe.
         The six head maps are the plan's static output buffers (3.8 MB per image), overwritten by the next call -- the same
         contract as `forward`."""
         B, _, H, W = x.shape
-        outs, dets = self.engine_for(B, H, W, decode_k=K, dets_only=dets_only).process(x)
+        extra = {"flip_test": True} if flip_test else {}      # the default calls stay exactly what they were
+        outs, dets = self.engine_for(B, H, W, decode_k=K, dets_only=dets_only, **extra).process(x)
         return outs, dets.clone()
 
     def pipeline_for(self, B, H, W, decode_k=100, depth=2, dets_only=False):

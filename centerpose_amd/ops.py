@@ -119,6 +119,11 @@ def marshal(fn, desc, ptrs, ints):
         return ptrs[:6] + ints + [ptrs[6]]
     if fn == "cp_head_points_f32":                # ptrs: feat, ws_inds, w1, b1, w2, b2, out; ints: featLd, B, H, W, C, J, K, hc
         return [ptrs[0], ints[0]] + ptrs[1:] + ints[1:]
+    if fn == "cp_flip_merge_pairs_f32":           # ptrs: in x4, out x4, perm, whole; ints: n, N, H, W, J, (C, mode) x4
+        ins = (ctypes.c_void_p * 4)(*[p.value for p in ptrs[:4]])
+        outs = (ctypes.c_void_p * 4)(*[p.value for p in ptrs[4:8]])
+        meta = (ctypes.c_int * 8)(*ints[5:13])
+        return [ints[0], ins, outs, meta] + ints[1:5] + [ptrs[8]]
     raise ValueError("unknown launch function %r" % fn)
 
 
@@ -126,7 +131,8 @@ FN_IDS = {"cp_conv2d_f32": 1, "cp_conv3x3_winograd_f32": 2, "cp_dcn_v2_f32": 3, 
           "cp_maxpool2d_nhwc_f32": 5, "cp_dw_deconv_add_nhwc_f32": 6, "cp_sum_up_nhwc_f32": 7, "cp_dwconv2d_nhwc_f32": 8,
           "cp_global_avgpool_nhwc_f32": 9, "cp_scale_add_nhwc_f32": 10, "cp_shuffle_concat_nhwc_f32": 11, "cp_head3x3_1x1_f32": 12,
           "cp_decode_topk_f32": 13, "cp_decode_assign_f32": 14, "cp_splitk_reduce_f32": 15, "cp_conv3x3_winograd24_group_f32": 16, "cp_conv2d_group_f32": 17,
-          "cp_sum_up_group_nhwc_f32": 18, "cp_head_points_f32": 19}
+          "cp_sum_up_group_nhwc_f32": 18, "cp_head_points_f32": 19,
+          "cp_flip_merge_pairs_f32": 20}
 
 
 def pad_rows(t, ldw):
@@ -742,3 +748,29 @@ def head_points_launch(feat, inds, w1, b1, w2, b2, out, *, hc, J, K):
     for t in (w1, b1, w2, b2):
         assert t.is_contiguous() and t.dtype == torch.float32
     return Launch("cp_head_points_f32", None, [feat, inds, w1, b1, w2, b2, out], [_ld(feat), B, H, W, C, J, K, hc], out_index=6)
+
+
+FLIP_MODES = {"flip": 0, "joints": 1, "offsets": 2, "copy": 3}     # cp_flip_merge_pairs_f32 modes (hm / wh, hm_hp, hps, reg / hp_offset)
+
+
+def flip_pairs_launch(maps, whole, perm):
+    """Up to four flip-test merges of N image / mirrored-twin pairs in ONE launch (cp_flip_merge_pairs_f32).  maps: list of
+    (src NCHW [2N,C,H,W] with image n at 2n and its twin at 2n + 1, out [N,C,H,W], mode); every `out` is a view of `whole`, the one
+    storage the dependency tracking sees as this launch's output; perm: the joint permutation, int32 bits in a float32 tensor [J]."""
+    n = len(maps)
+    assert 1 <= n <= 4
+    src0 = maps[0][0]
+    N2, _, H, W = src0.shape
+    assert N2 % 2 == 0 and perm.dtype == torch.float32 and perm.is_contiguous()
+    J = perm.numel()
+    meta = []
+    for src, out, mode in maps:
+        C = src.shape[1]
+        assert tuple(src.shape) == (N2, C, H, W) and tuple(out.shape) == (N2 // 2, C, H, W) and src.is_contiguous() and out.is_contiguous()
+        assert out.untyped_storage().data_ptr() == whole.untyped_storage().data_ptr() and mode in (0, 1, 2, 3)
+        meta += [C, mode]
+    pad = [None] * (4 - n)
+    meta += [0, 0] * (4 - n)
+    ins = [m[0] for m in maps] + pad
+    outs = [m[1] for m in maps] + pad
+    return Launch("cp_flip_merge_pairs_f32", None, ins + outs + [perm, whole], [n, N2 // 2, H, W, J] + meta)

@@ -18,7 +18,9 @@ Layout (all integers little-endian; offsets in bytes from the start of the file)
     u32      B, H, W        network input [B,3,H,W]
     u32      nbuf, nconst, nops, nout
     u32      meta_len       JSON (utf-8): {"arch", "flops_per_image", "ops": [{"kind", "name", "flops"}, ...]}, plus "dets_only": true
-                            for a detections-only plan (Engine(..., dets_only=True): outputs 1, 2, 3, 5 valid at the decoded peaks only)
+                            for a detections-only plan (Engine(..., dets_only=True): outputs 1, 2, 3, 5 valid at the decoded peaks only),
+                            "flip_test": true for a flip-test plan (Engine(..., flip_test=True): B = 2N images as N image / mirrored-twin
+                            pairs, the outputs un-merged [2N] maps, the decode over the N merged pairs)
     u32      checksum       FNV-1a (32 bit) of every byte behind this 48-byte header (CPPLAN04; 0 in older files).  It catches
                             truncation and bit rot.  A plan file is a TRUSTED artifact like a shared library: readers validate its
                             structure (arity, reference ranges, descriptor sizes), not every extent a kernel derives from it.
@@ -177,6 +179,8 @@ def plan_blob(engine, deterministic=False):
     meta = {"arch": engine.arch, "flops_per_image": int(engine.flops_per_image)}
     if getattr(engine, "dets_only", False):
         meta["dets_only"] = True          # outputs 1, 2, 3, 5 hold values at the decoded peaks only (cp_plan_dets_only)
+    if getattr(engine, "flip_test", False):
+        meta["flip_test"] = True          # batch = N image / twin pairs, dets [N, K, 5+3J] (cp_plan_flip_test)
     return serialize(launches, meta, engine.input, getattr(engine, "head_maps", engine.outputs), int(_lib.lib().cp_abi_version()), streams)
 
 
@@ -303,6 +307,7 @@ def load_plan(path, device="cuda", use_graph=True):
         eng.launches = launches
         eng.head_maps = [view(r).view(*shape) for r, shape in p["outputs"]]
         eng.dets_only = bool(p["meta"].get("dets_only", False))
+        eng.flip_test = bool(p["meta"].get("flip_test", False))
         # a detections-only plan: forward() hands out hm / hm_hp only (the other four maps are valid at the decoded peaks alone)
         eng.outputs = [None if eng.dets_only and i in (1, 2, 3, 5) else t for i, t in enumerate(eng.head_maps)]
         eng.flops_per_image = p["meta"]["flops_per_image"]

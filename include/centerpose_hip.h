@@ -193,6 +193,12 @@ int cp_fill_f32(float* p, float v, long long n, void* stream);
  * mode 0 = W-flip average (hm, wh); 1 = + left/right joint swap (hm_hp); 2 = swap on (x,y) pairs + negate x (hps).
  * perm: device int[J] joint permutation (NULL for mode 0). */
 int cp_flip_merge_f32(const float* in, float* out, int C, int H, int W, int mode, const int* perm, void* stream);
+/* the same merge for N image / mirrored-twin pairs and up to four maps in ONE launch: in[k] NCHW [2N,C_k,H,W] with image n at batch
+ * 2n and its twin at 2n + 1 -> out[k] [N,C_k,H,W]; meta: [n][2] = C_k, mode_k with modes 0..2 as above and 3 = copy of the image's
+ * own plane (reg, hp_offset: multi_pose.py:52-53).  Bit-identical to cp_flip_merge_f32 per pair.  perm: device int[J] (modes 1, 2:
+ * C_k = J resp. 2J).  W % 4 == 0 with 16-B aligned maps takes a float4 path, anything else a scalar one. */
+int cp_flip_merge_pairs_f32(int n, const float* const* in, float* const* out, const int* meta, int N, int H, int W, int J,
+                            const int* perm, void* stream);
 
 /* ---- device pre-/post-processing ---------------------------------------------------
  * The 8-bit pixel arithmetic is OpenCV's (opencv-python, unpinned, requirements.txt): resize.cpp / imgwarp.cpp fixed-point
@@ -252,8 +258,8 @@ int cp_head_points_f32(const float* feat, int featLd, const int* ws_inds, const 
 
 /* ---- plan handle: a whole network behind three calls -----------------------------
  * Replaces BackBoneWithHead.forward (lib/models/model.py:57-59: head_model(backbone_model(x))) for one compiled
- * (arch, B, H, W) and, with cp_plan_process, MultiPoseDetector.process (lib/detectors/multi_pose.py:29-60; flip test
- * excluded) -- no Python involved.  A plan file / blob (layout: centerpose_amd/plan.py; written by Engine.save_plan) holds
+ * (arch, B, H, W) and, with cp_plan_process, MultiPoseDetector.process (lib/detectors/multi_pose.py:29-60; the flip test
+ * through a plan compiled with it, see cp_plan_flip_test) -- no Python involved.  A plan file / blob (layout: centerpose_amd/plan.py; written by Engine.save_plan) holds
  * the packed, BN-folded, Winograd-transformed constants and the schedule of the launches above.
  * cp_plan_load / cp_plan_create are the ONLY entry points of this library that allocate device memory (activation
  * buffers, constants; owned by the handle, released by cp_plan_destroy) and they synchronise the device once.
@@ -278,6 +284,11 @@ int cp_plan_destroy(cp_plan* plan);
  * else 0 (-1: NULL plan).  Such a plan still has six outputs, but outputs 1, 2, 3 and 5 (wh, hps, reg, hp_offset) are valid only at
  * the peaks the plan's own decode found; cp_plan_process / cp_pipeline_process need K = the plan's decode_k. */
 int cp_plan_dets_only(const cp_plan* plan);
+/* 1 when the plan was compiled for the flip test (Engine(..., decode_k=K, flip_test=True): it holds a cp_flip_merge_pairs_f32
+ * launch), else 0 (-1: NULL plan).  Such a plan takes N image / mirrored-twin pairs as its batch B = 2N (image n at 2n, twin at
+ * 2n + 1); its six outputs are the un-merged [2N] maps, and cp_plan_process / cp_pipeline_process write dets [N,K,5+3J] and need
+ * K = the plan's decode_k. */
+int cp_plan_flip_test(const cp_plan* plan);
 
 /* ---- steps in flight (round 6): the C-ABI form of MultiPoseDetector.process_stream / engine.EnginePipeline ----------------------
  * Replaces nothing in the reference (it runs one image at a time, synchronously: lib/detectors/base_detector.py:79-140,
@@ -288,7 +299,8 @@ int cp_plan_dets_only(const cp_plan* plan);
  *   Engine(decode_k = K)) -> a handle that captures all their launch lists into ONE hipGraph on first use (both capture streams carry
  *   launches of several instances).  Does not take ownership of the plans; destroy the pipeline before its plans.
  * cp_pipeline_process: one replay = one step of EVERY instance.  images[k]: DEVICE float32 NCHW [B,3,H,W] (NULL = the caller filled
- *   cp_plan_input(plans[k]) itself); dets[k]: DEVICE float32 [B,K,5+3J] out; per instance bit-identical to cp_plan_process.
+ *   cp_plan_input(plans[k]) itself); dets[k]: DEVICE float32 [B,K,5+3J] out ([B/2,K,5+3J] for a flip-test plan); per instance
+ *   bit-identical to cp_plan_process.
  *   Enqueues on `stream`; the results of all instances are complete when the stream reaches the end of this call's work
  *   (throughput up, a batch's latency ~ depth x: INTEGRATION.md 3c). */
 typedef struct cp_pipeline cp_pipeline;
