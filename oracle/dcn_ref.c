@@ -2,11 +2,12 @@
  *
  * The reference has no CPU implementation of this op
  * (lib/models/backbones/DCNv2/src/cpu/dcn_v2_cpu.cpp:7-24 raises "Not implemented on the
- * CPU"), its extension cannot be built here (THC headers, CUDA only), and its own test
- * (DCNv2/test.py) stores no expected values.  DCN parity is therefore pinned only through
- * the reference's known-answer properties (zero-offset identity, test.py:31-66; integer
- * offsets == shifted taps; boundary rule) -- see tests/test_oracle_dcn.py -- and this
- * transliteration of the algorithm:
+ * CPU") and its extension needs CUDA, so this restatement is the checker that runs
+ * everywhere.  It is pinned to the reference's own im2col text, which oracle/Makefile
+ * compiles for the CPU where the reference tree is readable (oracle/_ref/libcp_refdcn.so):
+ * tests/test_dcn_reference_pin.py requires bit-equal columns and outputs within the
+ * reference's own rounding ambiguity, live and against tests/golden/dcn_ref_*.npz.  The
+ * known-answer properties (tests/test_oracle_dcn.py) stay.  Transliterated from:
  *
  *   bilinear sample   : src/cuda/dcn_v2_im2col_cuda.cu:25-54   (dmcn_im2col_bilinear)
  *   im2col + bounds   : src/cuda/dcn_v2_im2col_cuda.cu:125-195 (one (b,c,h,w) per thread,

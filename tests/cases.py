@@ -97,3 +97,323 @@ def flip_inputs(seed=41, H=12, W=20, J=17):
     return dict(hm=sigmoid(r.randn(2, 1, H, W)), wh=(r.rand(2, 2, H, W) * 30).astype(F32),
                 hps=(r.randn(2, 2 * J, H, W) * 8).astype(F32), reg=r.rand(2, 2, H, W).astype(F32),
                 hm_hp=sigmoid(r.randn(2, J, H, W) - 1.0), hp_offset=r.rand(2, 2, H, W).astype(F32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DCNv2 inputs.  Shared by the GPU kernel tests (tests/test_conv_hip.py), the reference pin (tests/test_dcn_reference_pin.py)
+# and tests/golden/make_golden_dcn.py, so that the committed reference outputs belong to exactly the inputs the kernel sees.
+# The seeds and the order of the draws are those the GPU tests have always used.
+
+def _dcn_case(seed, B, C, Co, H, W, big_offsets):
+    r = np.random.RandomState(seed)
+    x = r.randn(B, C, H, W).astype(np.float32)
+    w = (r.randn(Co, C, 3, 3) / (3 * C ** 0.5)).astype(np.float32)
+    b = r.randn(Co).astype(np.float32)
+    off = (r.randn(B, 18, H, W) * (4.0 if big_offsets else 1.0)).astype(np.float32)
+    if big_offsets:                     # far out-of-range and exactly-on-boundary samples
+        off[0, :, 0, 0] = 3 * H
+        off[0, :, 1, 1] = -3 * H
+        off[-1, 0::2, 2, 2] = -1.0      # h_im == integer boundary rows
+        off[-1, 1::2, 2, 3] = W
+    m = r.rand(B, 9, H, W).astype(np.float32)
+    return x, w, b, off, m
+
+
+def _dcn_mask_logits(seed, shape):
+    """Mask LOGITS for the om_sigmoid=True mode -- the mode every in-plan launch runs (engine.emit_dcn; the reference applies
+    torch.sigmoid to the mask third of conv_offset_mask's output, DCNv2/dcn_v2.py:117-127, then calls dcn_v2_forward): normal
+    logits plus saturating ones (|logit| > 20, +-90: exp overflows / underflows in float32).  -> (logits, sigmoid(logits)) with
+    the sigmoid evaluated by torch in float32 like the reference."""
+    import torch
+    r = np.random.RandomState(seed + 1000)
+    lg = (r.randn(*shape) * 3.0).astype(np.float32)
+    flat = lg.reshape(-1)
+    flat[0::17] = 25.0
+    flat[1::19] = -25.0
+    flat[2::23] = 90.0
+    flat[3::29] = -90.0
+    flat[4::31] = 0.0
+    return lg, torch.sigmoid(torch.from_numpy(lg)).numpy()
+
+
+def dcn_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw):
+    return (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+
+
+def _dcn_dict(x, w, b, off, m, args=(3, 3, 1, 1, 1, 1, 1, 1, 1), logits=None, relu=False, **extra):
+    """x, w, b, off, m: what dcn_v2_forward takes (m is the mask itself); args = (kh, kw, sh, sw, ph, pw, dh, dw, dg); logits: the
+    mask logits when the kernel test runs the sigmoid-inside mode; relu: the kernel test compares max(ref, 0)."""
+    return dict(x=x, w=w, b=b, off=off, m=m, args=tuple(int(a) for a in args), logits=logits, relu=relu, **extra)
+
+
+# test_dcn_v2_vs_scalar_oracle: (C, Co, H, W, big, tile)
+DCN_KERNEL_SHAPES = [(16, 64, 12, 10, True, 0), (64, 64, 16, 16, False, 128064), (32, 32, 9, 13, True, 128032), (128, 128, 8, 8, False, 64064),
+                     (64, 64, 11, 13, True, 64064), (32, 128, 9, 16, False, 64128), (16, 64, 9, 7, True, 64064), (48, 128, 6, 10, True, 64128),
+                     (128, 256, 8, 8, False, 64128), (32, 64, 12, 12, True, 128064), (96, 128, 6, 10, True, 64032), (48, 64, 5, 9, True, 64032),
+                     (128, 64, 11, 13, True, 0), (256, 64, 5, 6, True, 0)]
+# test_dcn_v2_split_k_vs_scalar_oracle: (C, Co, H, W, S, tile)
+DCN_SPLITK_SHAPES = [(64, 64, 9, 7, 3, 0), (32, 128, 6, 10, 9, 64128), (128, 256, 8, 8, 3, 64064), (48, 64, 5, 9, 2, 0)]
+# test_dcn_v2_kernel_deformable_groups_vs_scalar_oracle: (C, Co, dg, tile, S)
+DCN_KERNEL_DG_SHAPES = [(64, 64, 2, 0, 1), (128, 128, 4, 64128, 1), (64, 64, 2, 0, 3), (96, 64, 3, 128064, 1)]
+# test_dcn_v2_forward_deformable_groups: (C, Co, dg, k, s, p, d)
+DCN_FORWARD_DG_ROWS = [(32, 64, 2, 3, 1, 1, 1), (64, 64, 4, 3, 1, 1, 1), (96, 128, 2, 3, 2, 1, 1), (12, 7, 3, 3, 1, 2, 2),
+                       (20, 40, 2, 1, 1, 0, 1), (64, 32, 1, 3, 1, 1, 1)]
+# test_dcn_v2_forward_full_argument_space: (C, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg)
+DCN_FULL_ARG_ROWS = [(16, 24, 3, 3, 2, 1, 1, 2, 1, 2, 1), (32, 16, 1, 3, 1, 2, 0, 1, 1, 1, 2), (8, 12, 5, 5, 1, 1, 2, 2, 1, 1, 1),
+                     (16, 8, 3, 5, 2, 2, 3, 1, 2, 1, 1), (16, 16, 7, 7, 1, 1, 3, 3, 1, 1, 1)]
+
+
+def dcn_kernel_case(C, Co, H, W, big, tile=0, sig=False):
+    """Inputs of test_dcn_v2_vs_scalar_oracle[sig]."""
+    x, w, b, off, m = _dcn_case(C + H, 2, C, Co, H, W, big)
+    lg = None
+    if sig:
+        lg, m = _dcn_mask_logits(C + H, m.shape)
+    return _dcn_dict(x, w, b, off, m, logits=lg, tile=tile)
+
+
+def dcn_splitk_case(C, Co, H, W, S, tile=0, sig=False):
+    """Inputs of test_dcn_v2_split_k_vs_scalar_oracle (compared after ReLU)."""
+    x, w, b, off, m = _dcn_case(C + S, 2, C, Co, H, W, True)
+    lg = None
+    if sig:
+        lg, m = _dcn_mask_logits(C + S, m.shape)
+    return _dcn_dict(x, w, b, off, m, logits=lg, relu=True, tile=tile, S=S)
+
+
+def dcn_kernel_dg_case(C, Co, dg, tile=0, S=1):
+    """Inputs of test_dcn_v2_kernel_deformable_groups_vs_scalar_oracle (mask logits, compared after ReLU)."""
+    r = np.random.RandomState(C + dg + S)
+    B, H, W, kk = 2, 9, 12, 9
+    x = r.randn(B, C, H, W).astype(np.float32)
+    w = (r.randn(Co, C, 3, 3) / (3 * C ** 0.5)).astype(np.float32)
+    b = r.randn(Co).astype(np.float32)
+    off = (r.randn(B, 2 * dg * kk, H, W) * 3.0).astype(np.float32)
+    lg, m = _dcn_mask_logits(C + dg, (B, dg * kk, H, W))
+    return _dcn_dict(x, w, b, off, m, (3, 3, 1, 1, 1, 1, 1, 1, dg), logits=lg, relu=True, tile=tile, S=S)
+
+
+def dcn_forward_dg_case(C, Co, dg, k, s, p, d):
+    """Inputs of test_dcn_v2_forward_deformable_groups."""
+    r = np.random.RandomState(C * 3 + dg)
+    B, H, W = 2, 10, 13
+    Ho, Wo = dcn_out_hw(H, W, k, k, s, s, p, p, d, d)
+    x = r.randn(B, C, H, W).astype(np.float32)
+    w = (r.randn(Co, C, k, k) * 0.2).astype(np.float32)
+    b = r.randn(Co).astype(np.float32)
+    off = (r.randn(B, 2 * dg * k * k, Ho, Wo) * 2.5).astype(np.float32)
+    off[0, :, 0, 0] = 3 * H                     # far out of range in every group
+    off[-1, 0::2, 1, 1] = -1.0                  # on the boundary rule
+    m = r.rand(B, dg * k * k, Ho, Wo).astype(np.float32)
+    return _dcn_dict(x, w, b, off, m, (k, k, s, s, p, p, d, d, dg))
+
+
+def dcn_full_arg_case(C, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg):
+    """Inputs of test_dcn_v2_forward_full_argument_space."""
+    r = np.random.RandomState(C + 3 * kh + 5 * kw + sh)
+    B, H, W = 2, 12, 15
+    Ho, Wo = dcn_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+    kk = kh * kw
+    x = r.randn(B, C, H, W).astype(np.float32)
+    w = (r.randn(Co, C, kh, kw) * 0.2).astype(np.float32)
+    b = r.randn(Co).astype(np.float32)
+    off = (r.randn(B, 2 * dg * kk, Ho, Wo) * 2.0).astype(np.float32)
+    off[0, :, 0, 0] = 4 * H
+    off[-1, 0::2, -1, -1] = -1.0
+    m = r.rand(B, dg * kk, Ho, Wo).astype(np.float32)
+    return _dcn_dict(x, w, b, off, m, (kh, kw, sh, sw, ph, pw, dh, dw, dg))
+
+
+def dcn_gpu_fuzz_cases():
+    """The 24 cases of test_dcn_v2_forward_random_argument_fuzz, in its order."""
+    r = np.random.RandomState(2024)
+    out = []
+    while len(out) < 24:
+        dg = int(r.choice([1, 1, 2, 3]))
+        C = dg * int(r.choice([4, 8, 16, 24]))
+        Co = int(r.choice([3, 8, 17, 40]))
+        kh, kw = int(r.randint(1, 6)), int(r.randint(1, 6))
+        sh, sw = int(r.randint(1, 4)), int(r.randint(1, 4))
+        ph, pw = int(r.randint(0, 4)), int(r.randint(0, 4))
+        dh, dw = int(r.randint(1, 3)), int(r.randint(1, 3))
+        B, H, W = 2, int(r.randint(7, 15)), int(r.randint(7, 15))
+        Ho, Wo = dcn_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+        if Ho < 1 or Wo < 1:
+            continue
+        kk = kh * kw
+        x = r.randn(B, C, H, W).astype(np.float32)
+        w = (r.randn(Co, C, kh, kw) / np.sqrt(C * kk)).astype(np.float32)
+        b = r.randn(Co).astype(np.float32)
+        off = (r.randn(B, 2 * dg * kk, Ho, Wo) * 1.5).astype(np.float32)
+        m = r.rand(B, dg * kk, Ho, Wo).astype(np.float32)
+        out.append(_dcn_dict(x, w, b, off, m, (kh, kw, sh, sw, ph, pw, dh, dw, dg)))
+    return out
+
+
+def dcn_pin_fuzz_cases(n=240, seed=950):
+    """Seeded fuzz of the reference pin: kh, kw 1..5, stride 1..3, pad 0..3, dilation 1..3 per axis, dg 1..4, odd maps, B 1..3;
+    offsets N(0, 2.5) with a few far / on-the-lattice values, masks with exact 0 and 1."""
+    r = np.random.RandomState(seed)
+    out = []
+    while len(out) < n:
+        dg = int(r.randint(1, 5))
+        C = dg * int(r.choice([1, 2, 3, 5]))
+        Co = int(r.choice([1, 3, 8, 13]))
+        kh, kw = int(r.randint(1, 6)), int(r.randint(1, 6))
+        sh, sw = int(r.randint(1, 4)), int(r.randint(1, 4))
+        ph, pw = int(r.randint(0, 4)), int(r.randint(0, 4))
+        dh, dw = int(r.randint(1, 4)), int(r.randint(1, 4))
+        B, H, W = int(r.randint(1, 4)), 2 * int(r.randint(2, 8)) + 1, 2 * int(r.randint(2, 8)) + 1
+        Ho, Wo = dcn_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+        if Ho < 1 or Wo < 1:
+            continue
+        kk = kh * kw
+        x = r.randn(B, C, H, W).astype(np.float32)
+        w = (r.randn(Co, C, kh, kw) / np.sqrt(C * kk)).astype(np.float32)
+        b = r.randn(Co).astype(np.float32)
+        off = (r.randn(B, 2 * dg * kk, Ho, Wo) * 2.5).astype(np.float32)
+        flat = off.reshape(-1)
+        flat[0::13] = np.round(flat[0::13])          # integer offsets: samples exactly on the lattice and on the -1 / H lines
+        flat[1::37] = np.float32(3 * H)
+        flat[2::41] = np.float32(-1e6)
+        flat[3::43] = np.float32(-0.0)
+        m = r.rand(B, dg * kk, Ho, Wo).astype(np.float32)
+        m.reshape(-1)[0::11] = 0.0
+        m.reshape(-1)[1::11] = 1.0
+        out.append(_dcn_dict(x, w, b, off, m, (kh, kw, sh, sw, ph, pw, dh, dw, dg)))
+    return out
+
+
+# --- boundary lattice ------------------------------------------------------------------------------------------------
+# (name, stride, pad, dilation, dg): 3 x 3 taps on a 7 x 9 map
+DCN_LATTICE_CONFIGS = [("s1p1d1", 1, 1, 1, 1), ("s2p0d1", 2, 0, 1, 1), ("s2p2d1", 2, 2, 1, 1), ("s1p2d2", 1, 2, 2, 1),
+                       ("s2p0d2", 2, 0, 2, 1), ("s2p2d2", 2, 2, 2, 1), ("s1p1d1g2", 1, 1, 1, 2), ("s2p2d2g2", 2, 2, 2, 2)]
+DCN_LATTICE_HW = (7, 9)
+
+
+def dcn_lattice_targets(N):
+    """(label, coordinate, side) the sampling coordinate h_im (w_im) has to land on, for an axis of N rows (columns).  side 0: hit
+    it exactly; side +1 / -1: the float just above / below it.  These are the points where the reference's conditions switch
+    (dcn_v2_im2col_cuda.cu:28-48,180): `> -1`, `floor`, `h_low >= 0`, `h_high <= height - 1`, `< height`."""
+    N = float(N)
+    return [("-1", -1.0, 0), ("-1+", -1.0, +1), ("-0.5", -0.5, 0), ("0-", 0.0, -1), ("0", 0.0, 0), ("int", 2.0, 0), ("frac", 2.25, 0),
+            ("N-1", N - 1, 0), ("N-0.5", N - 0.5, 0), ("N-", N, -1), ("N", N, 0), ("N+0.5", N + 0.5, 0),
+            ("+3N", 3 * N, 0), ("-3N", -3 * N, 0), ("+1e6", 1e6, 0), ("-1e6", -1e6, 0)]
+
+
+def dcn_lattice_offset(base, t, side):
+    """The float32 offset that puts float32(base) + offset -- the reference's `h_in + i * dilation_h + offset_h`, an int plus a
+    float evaluated in float32 -- on the target: exactly on t (side 0; every t of the list is reachable exactly for |base| < 32), or
+    on the nearest reachable float strictly above (side +1) / below (side -1) t.  The sum is rounded, so for base != 0 the nearest
+    reachable neighbour of t can be a few ulps of t away."""
+    f = np.float32
+    base = f(base)
+    off = f(f(t) - base)
+    if side == 0:
+        assert f(base + off) == f(t), (base, t)
+        if base == 0 and t == 0:
+            off = f(-0.0)                # the -0.0 offset of the list: 0 + -0.0 is +0.0 in the reference's arithmetic
+        return off
+    for e in range(-100, 0):             # the smallest power-of-two step away from t that survives both roundings
+        off = f(float(t) + side * 2.0 ** e - float(base))
+        got = f(base + off)
+        if (side > 0 and got > f(t)) or (side < 0 and got < f(t)):
+            return off
+    raise AssertionError((base, t, side))
+
+
+def dcn_lattice_case(name, s, p, d, dg):
+    """Every 3 x 3 tap of every output position aims at one (h, w) target pair: each h target with an interior w (2.25), each w
+    target with an interior h, and each h target with the same-named w target (both conditions at once).  Batch images are added
+    until every pair has a position.  Distinct weight per (o, c, i, j), masks 0 / 1 / random.  Returns the case and, in
+    `h_im` / `w_im` [B, 9, Ho, Wo], the float32 coordinates the reference's expression evaluates to."""
+    H, W = DCN_LATTICE_HW
+    k, kk = 3, 9
+    Ho, Wo = dcn_out_hw(H, W, k, k, s, s, p, p, d, d)
+    th, tw = dcn_lattice_targets(H), dcn_lattice_targets(W)
+    inner = ("frac", 2.25, 0)
+    pairs = [(a, inner) for a in th] + [(inner, b) for b in tw] + list(zip(th, tw))
+    # which position aims at which pair: a "just above / below" target goes where some tap's integer part is 0 or -1 on that axis
+    # (there the exact float neighbour of the target is reachable), the rest fill up; images are added until every pair has a place
+    def near(q, n_out):
+        return [v for v in range(n_out) if any(v * s - p + i * d in (0, -1) for i in range(k))]
+    ys_ok, xs_ok = near(0, Ho), near(0, Wo)
+    place = {}
+    order = sorted(range(len(pairs)), key=lambda a: -(abs(pairs[a][0][2]) + abs(pairs[a][1][2])))
+    B = 0
+    for a in order:
+        (_, _, s_h), (_, _, s_w) = pairs[a]
+        pos = None
+        while pos is None:
+            free = [q for q in range(B * Ho * Wo) if q not in place]
+            good = [q for q in free if (not s_h or (q // Wo) % Ho in ys_ok) and (not s_w or q % Wo in xs_ok)]
+            if good:
+                pos = good[0]
+            else:
+                B += 1
+        place[pos] = a
+    for q in range(B * Ho * Wo):
+        place.setdefault(q, q % len(pairs))
+    C, Co = 2 * dg, 5
+    r = np.random.RandomState(7000 + 100 * s + 10 * p + d + 1000 * dg)
+    x = r.randn(B, C, H, W).astype(np.float32)
+    w = ((np.arange(Co * C * kk, dtype=np.float64).reshape(Co, C, k, k) % 89 - 44) / 64 + r.rand(Co, C, k, k) / 256).astype(np.float32)
+    b = r.randn(Co).astype(np.float32)
+    off = np.zeros((B, dg, kk, 2, Ho, Wo), np.float32)
+    h_im = np.zeros((B, dg, kk, Ho, Wo), np.float32)
+    w_im = np.zeros((B, dg, kk, Ho, Wo), np.float32)
+    for pos in range(B * Ho * Wo):
+        bi, y, xx = pos // (Ho * Wo), (pos // Wo) % Ho, pos % Wo
+        for g in range(dg):
+            (_, t_h, s_h), (_, t_w, s_w) = pairs[(place[pos] + g * (len(th) + 1)) % len(pairs)]     # the groups aim at different targets
+            for i in range(k):
+                for j in range(k):
+                    bh, bw = y * s - p + i * d, xx * s - p + j * d
+                    oh, ow = dcn_lattice_offset(bh, t_h, s_h), dcn_lattice_offset(bw, t_w, s_w)
+                    off[bi, g, i * k + j, 0, y, xx], off[bi, g, i * k + j, 1, y, xx] = oh, ow
+                    h_im[bi, g, i * k + j, y, xx] = np.float32(bh) + oh
+                    w_im[bi, g, i * k + j, y, xx] = np.float32(bw) + ow
+    m = (0.25 + 0.75 * r.rand(B, dg * kk, Ho, Wo)).astype(np.float32)
+    m.reshape(-1)[0::29] = 0.0
+    m.reshape(-1)[1::7] = 1.0
+    return _dcn_dict(x, w, b, off.reshape(B, 2 * dg * kk, Ho, Wo), m, (k, k, s, s, p, p, d, d, dg), name=name,
+                     h_im=h_im.reshape(B, dg * kk, Ho, Wo), w_im=w_im.reshape(B, dg * kk, Ho, Wo))
+
+
+def dcn_pin_groups():
+    """Every DCN input of the reference pin, by group: all inputs of the GPU suite's DCN tests, the lattice and the pin's own fuzz."""
+    return {
+        "kernel": [dcn_kernel_case(*row, sig=sig) for row in DCN_KERNEL_SHAPES for sig in (False, True)],
+        "split_k": [dcn_splitk_case(*row, sig=sig) for row in DCN_SPLITK_SHAPES for sig in (False, True)],
+        "kernel_dg": [dcn_kernel_dg_case(*row) for row in DCN_KERNEL_DG_SHAPES],
+        "forward_dg": [dcn_forward_dg_case(*row) for row in DCN_FORWARD_DG_ROWS],
+        "full_args": [dcn_full_arg_case(*row) for row in DCN_FULL_ARG_ROWS],
+        "gpu_fuzz": dcn_gpu_fuzz_cases(),
+        "lattice": [dcn_lattice_case(*row) for row in DCN_LATTICE_CONFIGS],
+        "pin_fuzz": dcn_pin_fuzz_cases(),
+    }
+
+
+# one kernel shape per tile code also in the logits mode (the smallest of each)
+DCN_FIXTURE_LOGITS_SHAPES = [(256, 64, 5, 6, True, 0), (16, 64, 9, 7, True, 64064), (48, 128, 6, 10, True, 64128), (32, 64, 12, 12, True, 128064),
+                             (32, 32, 9, 13, True, 128032), (48, 64, 5, 9, True, 64032)]
+
+
+def dcn_fixtures():
+    """name -> (zero-argument generator of the case) for every committed reference output tests/golden/dcn_ref_<name>.npz.  The
+    files hold the float32-rounded output of the reference forward (oracle.dcn.dcn_v2_forward_ref) only; inputs come from here."""
+    fx = {}
+    for row in DCN_KERNEL_SHAPES:
+        fx["kernel_%d_%d_%dx%d_mask" % row[:4]] = (lambda row=row: dcn_kernel_case(*row, sig=False))
+    for row in DCN_FIXTURE_LOGITS_SHAPES:
+        assert row in DCN_KERNEL_SHAPES
+        fx["kernel_%d_%d_%dx%d_logits" % row[:4]] = (lambda row=row: dcn_kernel_case(*row, sig=True))
+    for row in DCN_SPLITK_SHAPES:
+        fx["splitk_%d_%d_%dx%d_s%d" % row[:5]] = (lambda row=row: dcn_splitk_case(*row, sig=False))
+    for row in DCN_KERNEL_DG_SHAPES:
+        fx["kerneldg_%d_%d_g%d_s%d" % (row[0], row[1], row[2], row[4])] = (lambda row=row: dcn_kernel_dg_case(*row))
+    for row in DCN_FULL_ARG_ROWS:
+        fx["fullargs_" + "_".join(str(v) for v in row)] = (lambda row=row: dcn_full_arg_case(*row))
+    for row in DCN_LATTICE_CONFIGS:
+        fx["lattice_" + row[0]] = (lambda row=row: dcn_lattice_case(*row))
+    return fx

@@ -1,8 +1,9 @@
 """Golden vectors for the network forward: the REFERENCE modules (imported from /root/reference in
 the build container) run on the seeded synthetic checkpoint; outputs are committed as data.
-The DCNv2 arithmetic inside dla_34 comes from oracle/dcn.py plugged in as the reference's `_ext`
-(the reference has no CPU DCN and cannot be built here) -- the graph, BN, convs, deconvs, head are
-the reference's own code."""
+The DCNv2 forward inside the DCN backbones is oracle.dcn.ext_module(impl="ref") plugged in as the
+reference's `_ext`: the reference's own im2col text compiled for the CPU (oracle/Makefile), with a
+float64 GEMM standing in for cuBLAS -- so the graph, BN, convs, deconvs, head AND the deformable
+sampling are the reference's own code."""
 import os
 import sys
 import warnings
@@ -28,7 +29,7 @@ def ad(d):
 
 def build_reference(arch):
     from oracle import dcn
-    sys.modules["_ext"] = dcn.ext_module()
+    sys.modules["_ext"] = dcn.ext_module(impl="ref")
     from models.heads.keypoint import KeypointHead
 
     class M(torch.nn.Module):

@@ -6,6 +6,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import cases
+from cases import _dcn_case, _dcn_mask_logits
+
 pytestmark = pytest.mark.gpu
 
 
@@ -530,37 +533,6 @@ def test_channel_shuffle_concat(h):
     assert torch.equal(o[..., h:hp], torch.zeros(2, 5, 6, hp - h)) and torch.equal(o[..., hp + h:], torch.zeros(2, 5, 6, hp - h))
 
 
-def _dcn_case(seed, B, C, Co, H, W, big_offsets):
-    r = np.random.RandomState(seed)
-    x = r.randn(B, C, H, W).astype(np.float32)
-    w = (r.randn(Co, C, 3, 3) / (3 * C ** 0.5)).astype(np.float32)
-    b = r.randn(Co).astype(np.float32)
-    off = (r.randn(B, 18, H, W) * (4.0 if big_offsets else 1.0)).astype(np.float32)
-    if big_offsets:                     # far out-of-range and exactly-on-boundary samples
-        off[0, :, 0, 0] = 3 * H
-        off[0, :, 1, 1] = -3 * H
-        off[-1, 0::2, 2, 2] = -1.0      # h_im == integer boundary rows
-        off[-1, 1::2, 2, 3] = W
-    m = r.rand(B, 9, H, W).astype(np.float32)
-    return x, w, b, off, m
-
-
-def _dcn_mask_logits(seed, shape):
-    """Mask LOGITS for the om_sigmoid=True mode -- the mode every in-plan launch runs (engine.emit_dcn; the reference applies
-    torch.sigmoid to the mask third of conv_offset_mask's output, DCNv2/dcn_v2.py:117-127, then calls dcn_v2_forward): normal
-    logits plus saturating ones (|logit| > 20, +-90: exp overflows / underflows in float32).  -> (logits, sigmoid(logits)) with
-    the sigmoid evaluated by torch in float32 like the reference."""
-    r = np.random.RandomState(seed + 1000)
-    lg = (r.randn(*shape) * 3.0).astype(np.float32)
-    flat = lg.reshape(-1)
-    flat[0::17] = 25.0
-    flat[1::19] = -25.0
-    flat[2::23] = 90.0
-    flat[3::29] = -90.0
-    flat[4::31] = 0.0
-    return lg, torch.sigmoid(torch.from_numpy(lg)).numpy()
-
-
 def test_dcn_v2_split_k_vs_scalar_oracle():
     """cp_dcn_desc.ksplit: split-K over the taps into raw partial sums + cp_splitk_reduce_f32 (fixed-order sum, bias, ReLU) ==
     the scalar oracle; S = 3 and the extreme S = 9 (one tap per block), ragged M, 64- and 128-wide N tiles; twice -> same bits."""
@@ -890,6 +862,109 @@ def test_dcn_v2_kernel_deformable_groups_vs_scalar_oracle(C, Co, dg, tile, S):
     else:
         ops.dcn_v2(_nhwc(torch.from_numpy(x)), om.cuda(), wp, sc, sh, out, cout=Co, om_sigmoid=True, act=ops.ACT_RELU, tile=tile, dg=dg)
     _close(out.permute(0, 3, 1, 2), torch.from_numpy(ref), 1e-4)
+
+
+# --- the HIP kernel against the REFERENCE's own im2col text ------------------------------------------------------------------------
+# tests/golden/dcn_ref_<name>.npz: float32 outputs of oracle.dcn.dcn_v2_forward_ref (the reference's dmcn_im2col_bilinear /
+# modulated_deformable_im2col_gpu_kernel compiled for the CPU, GEMM in float64), made by tests/golden/make_golden_dcn.py; inputs from
+# tests/cases.py.  Same gate as the oracle tests above: 1e-4 * max|ref| (SURVEY 8d gate 2).  Worst errors: profiles/dcn_reference_pin.txt.
+
+_DCN_FIXTURES = cases.dcn_fixtures()
+
+
+def _dcn_golden(name, golden_dir):
+    import os
+    path = os.path.join(golden_dir, "dcn_ref_%s.npz" % name)
+    assert os.path.exists(path), "missing reference fixture " + path
+    with np.load(path) as z:
+        return z["out"]
+
+
+def _close_report(what, out, ref, tol=1e-4):
+    out, ref = out.detach().cpu().double(), torch.from_numpy(np.ascontiguousarray(ref)).double()
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    err, scale = (out - ref).abs().max().item(), max(ref.abs().max().item(), 1e-6)
+    print("\n%s: max err %.3e = %.3e of max|ref| %.3e (gate %.0e)" % (what, err, err / scale, scale, tol))
+    assert err <= tol * scale, "%s: max err %.3e (scale %.3e)" % (what, err, scale)
+
+
+def _dcn_kernel_run(c, tile, S=1, act=0):
+    """One cp_dcn launch (S == 1) or split-K launch + cp_splitk_reduce_f32 (S > 1) on a tests/cases.py DCN case -> NCHW view."""
+    from centerpose_amd import ops
+    x, w, b, off = c["x"], c["w"], c["b"], c["off"]
+    dg = c["args"][8]
+    sig = c["logits"] is not None
+    m_in = c["logits"] if sig else c["m"]
+    B, C, H, W = x.shape
+    Co, kk = w.shape[0], 9
+    om = torch.zeros(B, H, W, ops.round_up(3 * dg * kk, 4) if dg > 1 else 32)
+    om[..., :2 * dg * kk] = torch.from_numpy(off).permute(0, 2, 3, 1)
+    om[..., 2 * dg * kk:3 * dg * kk] = torch.from_numpy(m_in).permute(0, 2, 3, 1)
+    wp = ops.pack_conv_weight(torch.from_numpy(w).cuda())
+    sc, sh = ops.fold_bn(Co, None, torch.from_numpy(b).cuda())
+    out = torch.full((B, H, W, Co), float("nan"), device="cuda")
+    xs = _nhwc(torch.from_numpy(x))
+    if S > 1:
+        ldw = wp.shape[0]
+        ws = torch.full((S, B * H * W, ldw), float("nan"), device="cuda")
+        ops.dcn_v2_launch(xs, om.cuda(), wp, torch.ones(ldw, device="cuda"), torch.zeros(ldw, device="cuda"), ws, cout=ldw,
+                          om_sigmoid=sig, tile=tile, ksplit=S, dg=dg).run()
+        ops.splitk_reduce_launch(ws, sc, sh, out, cout=Co, act=act).run()
+    else:
+        ops.dcn_v2(xs, om.cuda(), wp, sc, sh, out, cout=Co, om_sigmoid=sig, act=act, tile=tile, dg=dg)
+    return out.permute(0, 3, 1, 2)
+
+
+@pytest.mark.parametrize("C,Co,H,W,big,tile,mode",
+                         [r + ("mask",) for r in cases.DCN_KERNEL_SHAPES] + [r + ("logits",) for r in cases.DCN_FIXTURE_LOGITS_SHAPES])
+def test_dcn_v2_vs_reference_golden(C, Co, H, W, big, tile, mode, golden_dir):
+    """Every shape of test_dcn_v2_vs_scalar_oracle in mask mode and one shape per tile code (0, 64064, 64128, 128064, 128032, 64032)
+    in logits mode (torch.sigmoid in float32 before the reference call, DCNv2/dcn_v2.py:117-127; the kernel applies its own)."""
+    name = "kernel_%d_%d_%dx%d_%s" % (C, Co, H, W, mode)
+    c = _DCN_FIXTURES[name]()
+    assert (c["logits"] is not None) == (mode == "logits")
+    _close_report(name, _dcn_kernel_run(c, tile), _dcn_golden(name, golden_dir))
+
+
+@pytest.mark.parametrize("C,Co,H,W,S,tile", cases.DCN_SPLITK_SHAPES)
+def test_dcn_v2_split_k_vs_reference_golden(C, Co, H, W, S, tile, golden_dir):
+    """Split-K over the taps + cp_splitk_reduce_f32 (bias, ReLU) against max(reference, 0)."""
+    from centerpose_amd import ops
+    name = "splitk_%d_%d_%dx%d_s%d" % (C, Co, H, W, S)
+    _close_report(name, _dcn_kernel_run(_DCN_FIXTURES[name](), tile, S, ops.ACT_RELU), np.maximum(_dcn_golden(name, golden_dir), 0.0))
+
+
+@pytest.mark.parametrize("C,Co,dg,tile,S", cases.DCN_KERNEL_DG_SHAPES)
+def test_dcn_v2_kernel_deformable_groups_vs_reference_golden(C, Co, dg, tile, S, golden_dir):
+    """cp_dcn_desc.dg > 1 (mask logits, ReLU; one row through split-K) against max(reference, 0)."""
+    from centerpose_amd import ops
+    name = "kerneldg_%d_%d_g%d_s%d" % (C, Co, dg, S)
+    _close_report(name, _dcn_kernel_run(_DCN_FIXTURES[name](), tile, S, ops.ACT_RELU), np.maximum(_dcn_golden(name, golden_dir), 0.0))
+
+
+@pytest.mark.parametrize("name", [n for n in sorted(_DCN_FIXTURES) if n.startswith(("fullargs_", "lattice_"))])
+@pytest.mark.parametrize("face", ["python", "pybind"])
+def test_dcn_v2_forward_vs_reference_golden(name, face, golden_dir):
+    """The full-argument-space rows and the boundary lattice (coordinates exactly on -1, just above it, 0, H-1, just below H, H, far
+    out: tests/cases.py::dcn_lattice_case) through both faces of the reference FFI."""
+    if face == "python":
+        from centerpose_amd import dcn_v2_ext as ext
+    else:
+        from centerpose_amd import _ext as ext
+    c = _DCN_FIXTURES[name]()
+    out = ext.dcn_v2_forward(*(torch.from_numpy(c[k]).cuda() for k in ("x", "w", "b", "off", "m")), *c["args"])
+    assert out.is_cuda
+    _close_report("%s[%s]" % (name, face), out, _dcn_golden(name, golden_dir))
+
+
+def test_dcn_reference_golden_all_used(golden_dir):
+    """No fixture is left out: the four tests above name every committed dcn_ref_*.npz."""
+    import os
+    used = {"kernel_%d_%d_%dx%d_mask" % r[:4] for r in cases.DCN_KERNEL_SHAPES} | {"kernel_%d_%d_%dx%d_logits" % r[:4] for r in cases.DCN_FIXTURE_LOGITS_SHAPES}
+    used |= {"splitk_%d_%d_%dx%d_s%d" % r[:5] for r in cases.DCN_SPLITK_SHAPES} | {"kerneldg_%d_%d_g%d_s%d" % (r[0], r[1], r[2], r[4]) for r in cases.DCN_KERNEL_DG_SHAPES}
+    used |= {n for n in _DCN_FIXTURES if n.startswith(("fullargs_", "lattice_"))}
+    have = {f[len("dcn_ref_"):-len(".npz")] for f in os.listdir(golden_dir) if f.startswith("dcn_ref_") and f.endswith(".npz")}
+    assert used == have == set(_DCN_FIXTURES)
 
 
 @pytest.mark.parametrize("cin,cout,hw,B", [(16, 16, (24, 40), 2), (16, 64, (8, 16), 1), (64, 64, (20, 28), 3), (32, 27, (16, 16), 2),
