@@ -14,6 +14,10 @@ source object, every pixel / tensor stage runs on the device:
   by construction, multi_pose.py:63) -- that is the batched throughput path of BASELINE.json;
 * ``post_process``: inverse affine of boxes / keypoints as one HIP kernel, one D2H copy;
 * ``merge_outputs``: soft-NMS on the host (C++, csrc/host_nms.cpp).
+
+``run_batch`` (not in the reference, which is one image at a time) takes N images through the same stages batched:
+``pre_process_batch`` / ``process`` / ``post_process_batch`` / ``merge_outputs_batch`` (csrc/batch_stages.hip), soft-NMS included
+on the device, with one upload and one download per call.
 """
 import ctypes
 import time
@@ -91,6 +95,66 @@ def _imread(path):
     return cv2.imread(path)
 
 
+# cp_pre_desc (include/centerpose_hip.h): one source image of a batched pre-process
+PRE_DESC = np.dtype([("src_off", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"),
+                     ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
+
+
+class _Staging:
+    """A pinned host buffer that grows on demand, and ONE stream-ordered upload of its first bytes per use.  `host()` waits for the
+    previous upload to have left the buffer before handing it out again (an event on that copy alone, not a device synchronisation)."""
+
+    def __init__(self):
+        self.buf = None
+        self.event = None
+
+    def host(self, nbytes):
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, pin_memory=True)
+        return self.buf.numpy()[:nbytes]
+
+    def upload(self, nbytes):
+        dev = torch.empty(int(nbytes), dtype=torch.uint8, device="cuda")
+        dev.copy_(self.buf[:nbytes], non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+        return dev
+
+
+def invert_warp(M):
+    """The inversion cv2.warpAffine applies to its 2x3 matrix, by the library's own double operations (cp_invert_warp: the ones
+    cp_preprocess_u8_f32 uses) -> float64 [6]."""
+    M = np.ascontiguousarray(M, np.float64).reshape(6)
+    Mi = np.empty(6, np.float64)
+    _lib.check(_lib.lib().cp_invert_warp(M.ctypes.data_as(ctypes.c_void_p), Mi.ctypes.data_as(ctypes.c_void_p)), "cp_invert_warp")
+    return Mi
+
+
+def post_merge_batch(dets, trans=None, scales=None, nms=False, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
+    """cp_post_merge_batch_f32: dets, a list of S device tensors [N,K,56] (one per scale) -> (rows [N,S*K,56], n_keep int32 [N]), both
+    on the device.  trans: device float64 [S,N,6] feature-map -> image affines with `scales` (S floats), or None for rows that are
+    mapped already; nms: soft_nms_39 per image with the given parameters (at most 512 rows per image)."""
+    S = len(dets)
+    if S < 1 or any(d.dim() != 3 or d.shape != dets[0].shape or d.shape[2] != 56 for d in dets):
+        raise _lib.CenterposeHipError("post_merge_batch expects per scale one [N,K,56] tensor of the same shape")
+    dets = [_lib.f32(d.detach(), "dets").contiguous() for d in dets]
+    N, K = int(dets[0].shape[0]), int(dets[0].shape[1])
+    if trans is not None and (trans.dtype != torch.float64 or tuple(trans.shape) != (S, N, 6) or scales is None or len(scales) != S):
+        raise _lib.CenterposeHipError("post_merge_batch: trans must be float64 [S,N,6] with S scales")
+    out = torch.empty((N, S * K, 56), dtype=torch.float32, device=dets[0].device)
+    n_keep = torch.empty((N,), dtype=torch.int32, device=dets[0].device)
+    ptrs = (ctypes.c_void_p * S)(*[_lib.ptr(d).value for d in dets])
+    sc = (ctypes.c_float * S)(*[float(v) for v in (scales if trans is not None else [1.0] * S)])
+    rc = _lib.lib().cp_post_merge_batch_f32(S, ptrs, _lib.ptr(trans.contiguous()) if trans is not None else None, sc, N, K, _lib.ptr(out),
+                                            _lib.c_void_p(n_keep.data_ptr()), 1 if nms else 0, _lib.c_float(sigma), _lib.c_float(Nt),
+                                            _lib.c_float(threshold), int(method), _lib.stream())
+    _lib.check(rc, "cp_post_merge_batch_f32")
+    return out, n_keep
+
+
 class BaseDetector(object):
     def __init__(self, cfg):
         print("Creating model...")
@@ -155,6 +219,174 @@ class BaseDetector(object):
 
     def merge_outputs(self, detections):
         raise NotImplementedError
+
+    # -- N images at once ------------------------------------------------------------------------------------------------
+    def _staging(self, which):
+        st = self.__dict__.setdefault("_staging_buffers", {})
+        if which not in st:
+            st[which] = _Staging()
+        return st[which]
+
+    @staticmethod
+    def _check_batch(images):
+        images = list(images)
+        for im in images:
+            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] > 0
+                    and im.shape[1] > 0):
+                raise _lib.CenterposeHipError("run_batch / pre_process_batch expect HxWx3 uint8 arrays (cv2.imread layout); there is no host fallback")
+        return images
+
+    @staticmethod
+    def _batch_layout(shapes):
+        """Byte offset of every image in the one staging buffer (images back to back) and the buffer's size."""
+        offsets, pos = [], 0
+        for h, w in shapes:
+            offsets.append(pos)
+            pos += h * w * 3
+        return offsets, pos
+
+    def _batch_groups(self, shapes):
+        """Indices of the images grouped by the network input shape they get at every TEST_SCALES entry (one batch per group and scale),
+        groups in order of first appearance, indices ascending.  FIX_RES: one group."""
+        groups = {}
+        for i, (h, w) in enumerate(shapes):
+            key = tuple(self.input_geometry(h, w, scale)[2:4] for scale in self.scales)
+            groups.setdefault(key, []).append(i)
+        return list(groups.values())
+
+    def _pre_table(self, shapes, offsets, idx, scale):
+        """The descriptor table (PRE_DESC) of one batched pre-process: images `idx` at `scale`, which must share one network input shape
+        -> (table, scratch_bytes, inp_h, inp_w, metas).  Geometry, matrix and meta per image are pre_process's."""
+        nb = 2 if self.cfg.TEST.FLIP_TEST else 1
+        down = self.cfg.MODEL.DOWN_RATIO
+        table = np.zeros(len(idx), PRE_DESC)
+        metas, scratch, inp = [], 0, None
+        for j, i in enumerate(idx):
+            height, width = shapes[i]
+            new_h, new_w, inp_h, inp_w, c, s = self.input_geometry(height, width, scale)
+            if new_h <= 0 or new_w <= 0:
+                raise _lib.CenterposeHipError("image %d x %d at scale %s has no pixels" % (height, width, scale))
+            if inp is None:
+                inp = (inp_h, inp_w)
+            elif inp != (inp_h, inp_w):
+                raise _lib.CenterposeHipError("pre_process_batch needs one network input shape per call (%s and %s at scale %s): "
+                                              "run_batch groups mixed sizes" % (inp, (inp_h, inp_w), scale))
+            d = table[j]
+            d["src_off"], d["H"], d["W"], d["NH"], d["NW"], d["slot"] = offsets[i], height, width, new_h, new_w, nb * j
+            if (new_h, new_w) != (height, width):
+                d["mid_off"] = scratch
+                scratch += new_h * new_w * 3
+            else:
+                d["mid_off"] = -1
+            d["mi"] = invert_warp(get_affine_transform(c, s, 0, [inp_w, inp_h]))
+            metas.append({"c": c, "s": s, "out_height": inp_h // down, "out_width": inp_w // down})
+        return table, scratch, inp[0], inp[1], metas
+
+    @staticmethod
+    def _inverse_affines(metas):
+        """float64 [N,6]: post_process's feature-map -> image matrix per image."""
+        return np.stack([np.ascontiguousarray(get_affine_transform(m["c"], m["s"], 0, (m["out_width"], m["out_height"]), inv=1),
+                                              np.float64).reshape(6) for m in metas])
+
+    def _upload_images(self, images, offsets, nbytes):
+        """The N images into the pinned staging buffer, ONE host-to-device copy -> device uint8 [nbytes]."""
+        st = self._staging("images")
+        host = st.host(nbytes)
+        for im, off in zip(images, offsets):
+            host[off:off + im.size] = im.reshape(-1)
+        return st.upload(nbytes)
+
+    def _upload_table(self, parts):
+        """Host arrays (descriptor tables, affines; 8-byte items) back to back in the pinned table buffer, ONE copy -> the device
+        uint8 views of the parts."""
+        raw = [np.ascontiguousarray(p).view(np.uint8).reshape(-1) for p in parts]
+        st = self._staging("table")
+        host = st.host(sum(r.size for r in raw))
+        pos, spans = 0, []
+        for r in raw:
+            host[pos:pos + r.size] = r
+            spans.append((pos, r.size))
+            pos += r.size
+        dev = st.upload(pos)
+        return [dev[a:a + n] for a, n in spans]
+
+    def _launch_pre(self, staging, table_dev, table, scratch_bytes, inp_h, inp_w):
+        """cp_preprocess_batch_u8_f32 for one table -> float32 [nb * N, 3, inp_h, inp_w] on the device."""
+        nb = 2 if self.cfg.TEST.FLIP_TEST else 1
+        n = len(table)
+        x = torch.empty((nb * n, 3, inp_h, inp_w), dtype=torch.float32, device="cuda")
+        scratch = torch.empty((max(scratch_bytes, 1),), dtype=torch.uint8, device="cuda")
+        mean = np.ascontiguousarray(self.mean.reshape(3), np.float32)
+        std = np.ascontiguousarray(self.std.reshape(3), np.float32)
+        table = np.ascontiguousarray(table)
+        rc = _lib.lib().cp_preprocess_batch_u8_f32(
+            ctypes.c_void_p(staging.data_ptr()), ctypes.c_size_t(staging.numel()), ctypes.c_void_p(scratch.data_ptr()),
+            ctypes.c_size_t(scratch_bytes), ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, _lib.ptr(x),
+            nb * n, inp_h, inp_w, mean.ctypes.data_as(ctypes.c_void_p), std.ctypes.data_as(ctypes.c_void_p), 1 if nb == 2 else 0,
+            _lib.stream())
+        _lib.check(rc, "cp_preprocess_batch_u8_f32")
+        return x
+
+    def pre_process_batch(self, images, scale):
+        """pre_process for N images that share one network input shape at `scale` (any sizes with FIX_RES) -> (float32
+        [nb * N, 3, inp_h, inp_w] ON THE DEVICE, list of N meta dicts); nb = 2 with FLIP_TEST: image n at 2n, its mirrored twin at
+        2n + 1, the layout `process` takes.  One upload of the images, one of the descriptor table, one resize launch (if any image
+        is resized) and one warp launch; every image bit-identical to pre_process(image, scale)."""
+        images = self._check_batch(images)
+        if not images:
+            raise _lib.CenterposeHipError("pre_process_batch needs at least one image")
+        shapes = [im.shape[0:2] for im in images]
+        offsets, nbytes = self._batch_layout(shapes)
+        table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale)
+        staging = self._upload_images(images, offsets, nbytes)
+        table_dev, = self._upload_table([table])
+        return self._launch_pre(staging, table_dev, table, scratch_bytes, inp_h, inp_w), metas
+
+    def _process_batch(self, images):
+        raise NotImplementedError
+
+    def post_process_batch(self, dets, metas, scale=1):
+        raise NotImplementedError
+
+    def merge_outputs_batch(self, detections):
+        raise NotImplementedError
+
+    def run_batch(self, images):
+        """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
+        One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
+        shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
+        launch per group (soft-NMS on the device when TEST.NMS or several scales); ONE download.  The download is the only
+        synchronisation, so there are no stage timers: run() is the timed form.  With FLIP_TEST and a head gated off by cfg.LOSS
+        `process` takes one pair at a time; the stages around it stay batched."""
+        images = self._check_batch(images)
+        if not images:
+            return []
+        shapes = [im.shape[0:2] for im in images]
+        offsets, nbytes = self._batch_layout(shapes)
+        groups = self._batch_groups(shapes)
+        work, parts = [], []
+        for idx in groups:
+            for scale in self.scales:
+                table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, idx, scale)
+                work.append((table, scratch_bytes, inp_h, inp_w))
+                parts += [table, self._inverse_affines(metas)]
+        staging = self._upload_images(images, offsets, nbytes)
+        parts = self._upload_table(parts)
+        merged = []
+        for g, idx in enumerate(groups):
+            per_scale = []
+            for k, scale in enumerate(self.scales):
+                j = g * len(self.scales) + k
+                table, scratch_bytes, inp_h, inp_w = work[j]
+                x = self._launch_pre(staging, parts[2 * j], table, scratch_bytes, inp_h, inp_w)
+                dets = self._process_batch(x)
+                per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
+            merged.append(self.merge_outputs_batch(per_scale))
+        rows = (merged[0] if len(merged) == 1 else torch.cat(merged, 0)).cpu().numpy()          # the one download
+        results = [None] * len(images)
+        for r, i in enumerate(i for idx in groups for i in idx):
+            results[i] = {1: rows[r].tolist()}
+        return results
 
     def _source(self, x):
         if isinstance(x, np.ndarray):
@@ -319,6 +551,38 @@ class MultiPoseDetector(BaseDetector):
                                               _lib.c_float(float(scale)), _lib.stream())
         _lib.check(rc, "cp_transform_dets_f32")
         return {1: mapped[0].cpu().numpy()}
+
+    def _process_batch(self, images):
+        """`process` of a whole group -> dets [N,K,56].  FLIP_TEST with a head gated off by cfg.LOSS: the two-stage path takes exactly
+        one image / twin pair, so the pairs go through it one by one."""
+        if self.cfg.TEST.FLIP_TEST and not self._flip_replay_path():
+            return torch.cat([self.process(images[2 * n:2 * n + 2])[1] for n in range(images.shape[0] // 2)], 0)
+        return self.process(images)[1]
+
+    def _launch_post(self, dets, inv_dev, scale):
+        if self.num_classes != 1 or dets.dim() != 3 or dets.shape[2] != 56:
+            raise _lib.CenterposeHipError("multi_pose post_process handles one class and 17 joints (dets [N,K,56])")
+        return post_merge_batch([dets], trans=inv_dev, scales=[float(scale)])[0]
+
+    def post_process_batch(self, dets, metas, scale=1):
+        """post_process for N images: dets [N,K,56] on the device, one meta per image -> device float32 [N,K,56], row block n
+        bit-identical to post_process(dets[n:n + 1], metas[n], scale)[1].  No download."""
+        if dets.dim() != 3 or dets.shape[0] != len(metas):
+            raise _lib.CenterposeHipError("post_process_batch needs dets [N,K,56] and N metas")
+        inv_dev, = self._upload_table([self._inverse_affines(metas)])
+        return self._launch_post(dets, inv_dev.view(torch.float64).view(1, len(metas), 6), scale)
+
+    def merge_outputs_batch(self, detections):
+        """merge_outputs for N images: a list with one device [N,K,56] per scale (post_process_batch) -> device [N,S*K,56], the scales
+        stacked per image; soft_nms_39(Nt=0.5, method=2) per image ON THE DEVICE when TEST.NMS or several scales (multi_pose.py:73-79).
+        All S*K rows come back, as merge_outputs returns them.  Against merge_outputs: every column but the score bit-equal, the score
+        within the last float bit per Gaussian decay (the device's double exp).  At most 512 rows per image."""
+        detections = list(detections)
+        if self.cfg.TEST.NMS or len(self.cfg.TEST.TEST_SCALES) > 1:
+            return post_merge_batch(detections, nms=True, Nt=0.5, method=2)[0]
+        if len(detections) == 1:
+            return detections[0]
+        return post_merge_batch(detections)[0]
 
     def merge_outputs(self, detections):
         """multi_pose.py:73-79: rows of every scale stacked; soft-NMS when configured or when several scales were run."""

@@ -311,6 +311,39 @@ int cp_pipeline_destroy(cp_pipeline* pipe);
 /* stream-ordered device-to-device copy (for callers that keep a plan's outputs beyond the next forward) */
 int cp_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
 
+/* ---- the stages around the network for N images at once (MultiPoseDetector.run_batch) ---------------------------------------------
+ * cp_pre_desc: one source image of a batched pre-process.  src_off: byte offset of its uint8 [H,W,3] pixels in ONE staging buffer;
+ *   (NH,NW): the size cv2.resize brings it to (base_detector.py:47), mid_off: byte offset of that resized image in a scratch buffer,
+ *   or < 0 when (NH,NW) == (H,W) (no resize); mi: the INVERTED 2x3 warp matrix (destination pixel -> resized-image coordinates),
+ *   what cp_invert_warp makes of the matrix given to warpAffine -- the double operations of cp_preprocess_u8_f32; slot: the image's
+ *   index in the output batch (its mirrored twin goes to slot + 1).
+ * cp_preprocess_batch_u8_f32: cp_resize_u8 + cp_preprocess_u8_f32 for N images of different sizes and one network input size OH x OW:
+ *   one resize launch (when any image has mid_off >= 0) and one warp launch, bit-identical to the per-image calls.  staging / scratch:
+ *   DEVICE uint8 buffers of the given sizes; table: DEVICE cp_pre_desc[N], table_host: the same N descriptors on the HOST (every
+ *   offset, size and slot is checked against the buffer sizes and out_batch before anything is launched); out: DEVICE float32
+ *   [out_batch,3,OH,OW]; flip != 0 writes the twins.  OW % 4 == 0 with a 16-B aligned `out` takes a float4 store path.
+ * cp_post_merge_batch_f32: for S <= 4 scales DEVICE dets[s] [N,K,56] -> out [N,S*K,56] (scale-major per image, as merge_outputs
+ *   concatenates) and n_keep [N] (DEVICE int).  trans: DEVICE double [S][N][6], the feature-map -> image affine per (scale, image),
+ *   with scales HOST float[S]: cp_transform_dets_f32's arithmetic; NULL: the rows are copied as they are.  nms != 0: soft_nms_39 per
+ *   image on the device, one workgroup per image with its rows in LDS, cp_soft_nms_39's quirks kept (columns 0..38 move, 39..55 stay;
+ *   copy of 0..4 and swap of 5..38 on a discard; all S*K rows are written, the kept ones first).  Bit-equal to cp_soft_nms_39 except
+ *   that the Gaussian weight of method 2 uses the device's double exp (a decayed score may differ in its last float bit per decay).
+ *   At most cp_post_merge_max_rows() = 512 rows per image with nms; more is an argument error.  Without nms n_keep[n] = S*K. */
+typedef struct cp_pre_desc {
+    long long src_off, mid_off;
+    int H, W, NH, NW;
+    double mi[6];
+    int slot, pad;
+} cp_pre_desc;
+int cp_sizeof_pre_desc(void);
+int cp_invert_warp(const double* M, double* Mi);
+int cp_preprocess_batch_u8_f32(const unsigned char* staging, size_t staging_bytes, unsigned char* scratch, size_t scratch_bytes,
+                               const void* table, const void* table_host, int N, float* out, int out_batch, int OH, int OW,
+                               const float* mean, const float* std_, int flip, void* stream);
+int cp_post_merge_max_rows(void);
+int cp_post_merge_batch_f32(int S, const float* const* dets, const double* trans, const float* scales, int N, int K, float* out,
+                            int* n_keep, int nms, float sigma, float Nt, float threshold, int method, void* stream);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
