@@ -154,28 +154,21 @@ class PlanBuilder(nets.Graph):
     def bn(self, name):
         return tuple(self.w("%s.%s" % (name, s)) for s in ("weight", "bias", "running_mean", "running_var"))
 
-    def wino(self, wp, cin, cout, k=3, stride=1, pad=1, nsrc=1, key=None, hw=None):
-        """Winograd-domain weights for an eligible 3x3/s1/p1 layer, else None (direct kernel).  `key` (the layer's parameter
-        name): share the transformed weights between the plans of one model.  hw = (H, W) of the layer: lets
-        `ops.wino24_wanted` pick the F(2x4,3x3) kernel -> ("wino24", weights)."""
-        if self.winograd and hw is not None and ops.wino_eligible(cin, k, stride, pad, nsrc) and \
-                ops.wino24_wanted(self.B, hw[0], hw[1], cin, cout):
-            ck = ("u24", key, cin, cout)
-            hit = self.const_cache.get(ck) if key is not None else None
-            if hit is None:
-                hit = ops.pack_wino24_weight(wp, cin, cout)
-                if key is not None:
-                    self.const_cache[ck] = hit
-            return ("wino24", hit)
-        if self.winograd and ops.wino_eligible(cin, k, stride, pad, nsrc):
-            ck = ("u", key, cin, cout)
-            hit = self.const_cache.get(ck) if key is not None else None
-            if hit is None:
-                hit = ops.pack_wino_weight(wp, cin, cout)
-                if key is not None:
-                    self.const_cache[ck] = hit
-            return hit
-        return None
+    def wino_weight(self, kind, key, wp, cin, cout):
+        """Winograd-domain weights of the packed 3x3 weights `wp`: kind "wino" = F(2x2,3x3), "wino24" = F(2x4,3x3).  `key` (the
+        layer's parameter name): the transformed weights are shared between the plans of one model through const_cache."""
+        ck = ("u24" if kind == "wino24" else "u", key, cin, cout)
+        if ck not in self.const_cache:
+            self.const_cache[ck] = (ops.pack_wino24_weight if kind == "wino24" else ops.pack_wino_weight)(wp, cin, cout)
+        return self.const_cache[ck]
+
+    def wino(self, wp, cin, cout, key, k=3, stride=1, pad=1, nsrc=1, hw=None):
+        """(launch kind, Winograd-domain weights) for an eligible 3x3/s1/p1 layer, else None (direct kernel).  The kind is "wino"
+        (F(2x2,3x3)) unless hw = (H, W) of the layer is given and `ops.wino24_wanted` picks the F(2x4,3x3) kernel: "wino24"."""
+        if not (self.winograd and ops.wino_eligible(cin, k, stride, pad, nsrc)):
+            return None
+        kind = "wino24" if hw is not None and ops.wino24_wanted(self.B, hw[0], hw[1], cin, cout) else "wino"
+        return kind, self.wino_weight(kind, key, wp, cin, cout)
 
     def add(self, kind, name, flops, launch):
         self.launches.append((kind, name, flops * self.B, launch))
@@ -188,28 +181,40 @@ class PlanBuilder(nets.Graph):
             hit = self.const_cache[("unit", n)] = (torch.ones(n, device=self.dev), torch.zeros(n, device=self.dev))
         return hit
 
-    def add_wino(self, name, flops, x, wp, u, sc, sh, out, cout, act, res=None):
-        """One Winograd 3x3 launch -- or, for a map too small to fill the chip (ops.wino_ksplit) and no residual, a split-C
-        launch into a workspace of raw partial outputs plus the fixed-order reduction that applies scale / shift / activation.
-        `u` = F(2x2) weights, or ("wino24", F(2x4) weights) from `self.wino` for the layers `ops.wino24_wanted` picks."""
+    def add_split(self, kind, name, suffix, flops, S, M, ld, make_launch, sc, sh, out, cout, act):
+        """A launch that cannot fill the chip as two: `make_launch(ones, zeros, workspace [S, M, ld])`, S splits storing raw partial
+        sums, then the fixed-order reduction `name + suffix` that applies scale / shift / activation (deterministic)."""
+        ws = self.pool.take(S * M * ld)
+        wst = ws[: S * M * ld].view(S, M, ld)
+        ones, zeros = self.unit_scale(sc.numel())
+        self.add(kind, name, flops, make_launch(ones, zeros, wst))
+        self.add("sum", name + suffix, 0, ops.splitk_reduce_launch(wst, sc, sh, out, cout=cout, act=act))
+        self.pool.give(ws)
+
+    def add_conv3x3(self, name, flops, x, wp, u, sc, sh, out, cout, act, res=None, splitc=True):
+        """One 3x3 / stride-1 / pad-1 launch on the kernel `u` = `self.wino(...)` names (None: the direct one) -- or, with `splitc`, for
+        an F(2x2) launch without residual on a map too small to fill the chip (ops.wino_ksplit), a split-C launch plus its reduction
+        (splitc=False: the head 3x3 launches of `emit_head` are never split)."""
+        kind, wu = u if u is not None else ("conv", None)
+        kw = dict(kh=3, kw=3, stride=1, pad=1, cout=cout, wino=wu, tile=ops.WINO24 if kind == "wino24" else 0)
         B, H, W, cin = x.shape
-        if isinstance(u, tuple):
-            self.add("wino24", name, flops, ops.conv2d_launch([x], wp, sc, sh, out, kh=3, kw=3, stride=1, pad=1, cout=cout, act=act,
-                                                              res=res, wino=u[1], tile=ops.WINO24))
-            return
-        S = ops.wino_ksplit(B, H, W, cin, cout) if (self.wino_splitc and res is None) else 1
+        S = ops.wino_ksplit(B, H, W, cin, cout) if (splitc and kind == "wino" and self.wino_splitc and res is None) else 1
         if S > 1:
-            ld, M = out.shape[3], B * H * W
-            ws = self.pool.take(S * M * ld)
-            wst = ws[: S * M * ld].view(S, M, ld)
-            ones, zeros = self.unit_scale(sc.numel())
-            self.add("wino", name, flops, ops.conv2d_launch([x], wp, ones, zeros, wst, kh=3, kw=3, stride=1, pad=1, cout=cout, wino=u,
-                                                            ksplit=S))
-            self.add("sum", name + ".splitc", 0, ops.splitk_reduce_launch(wst, sc, sh, out, cout=cout, act=act))
-            self.pool.give(ws)
-            return
-        self.add("wino", name, flops, ops.conv2d_launch([x], wp, sc, sh, out, kh=3, kw=3, stride=1, pad=1, cout=cout, act=act, res=res,
-                                                        wino=u))
+            self.add_split(kind, name, ".splitc", flops, S, B * H * W, out.shape[3], lambda ones, zeros, ws: ops.conv2d_launch(
+                [x], wp, ones, zeros, ws, ksplit=S, **kw), sc, sh, out, cout, act)
+        else:
+            self.add(kind, name, flops, ops.conv2d_launch([x], wp, sc, sh, out, act=act, res=res, **kw))
+
+    def group_bufs(self, shapes):
+        """Activations of (H, W, C, Cp) = logical / physical channels each, carved from ONE pool slot -> (the activations, the view
+        of the whole storage for the grouped launch that writes them).  A launch record has a single output storage, which is what
+        `Engine.dependencies` tracks; the slot returns to the pool when the last member activation is dropped."""
+        sizes = [self.B * H * W * Cp for H, W, _, Cp in shapes]
+        slot = self.pool.take(sum(sizes))
+        holder = Act(1, 1, 1, slot)
+        weakref.finalize(holder, self.pool.give, slot)
+        whole = slot[:sum(sizes)]
+        return [Act(H, W, C, v.view(self.B, H, W, Cp), parent=holder) for (H, W, C, Cp), v in zip(shapes, whole.split(sizes))], whole
 
     # -- emit hooks ---------------------------------------------------------------------------
     def emit_conv(self, xs, conv, bn, bias, co, k, stride, pad, relu, res, stem):
@@ -229,58 +234,39 @@ class PlanBuilder(nets.Graph):
         rt = res.t if res is not None else None
         ci = sum(a.C for a in xs)
         cip = ci if stem else sum(a.t.shape[3] for a in xs)               # physical K per tap
-        u = None if stem else self.wino(wp, cip, co, k, stride, pad, len(xs), key=conv, hw=(x.H, x.W))
+        u = None if stem else self.wino(wp, cip, co, conv, k, stride, pad, len(xs), hw=(x.H, x.W))
         flops = 2 * Ho * Wo * co * ci * k * k
-        if u is not None:
-            self.add_wino(conv, flops, srcs[0], wp, u, sc, sh, out.t, out.t.shape[3], self.act_code(relu), rt)
-            return out
         S = ops.conv_ksplit(ops.rule_batch(self.B) * Ho * Wo, wp.shape[0], wp.shape[1]) \
             if (self.conv_splitk and not stem and len(xs) == 1 and res is None and not (k == 3 and stride == 1 and pad == 1)) else 1
-        if S > 1:
-            # small-M launch (res_50 layer4 at B = 8: 256 blocks on 256 CUs): split-K into a workspace of raw partial sums, then the
-            # fixed-order reduction + BN + activation (deterministic; two launches)
-            ldw, M = wp.shape[0], self.B * Ho * Wo
-            ws = self.pool.take(S * M * ldw)
-            wst = ws[: S * M * ldw].view(S, M, ldw)
-            ones, zeros = self.unit_scale(ldw)
-            self.add("conv", conv, flops, ops.conv2d_launch(srcs, wp, ones, zeros, wst, kh=k, kw=k, stride=stride, pad=pad, cout=ldw, ksplit=S))
-            self.add("sum", conv + ".splitk", 0, ops.splitk_reduce_launch(wst, sc, sh, out.t, cout=out.t.shape[3], act=self.act_code(relu)))
-            self.pool.give(ws)
-            return out
-        self.add("conv", conv, flops,
-                 ops.conv2d_launch(srcs, wp, sc, sh, out.t, kh=k, kw=k, stride=stride, pad=pad, cout=out.t.shape[3],
-                                   act=self.act_code(relu), res=rt, in_nchw=stem))
+        if u is not None:
+            self.add_conv3x3(conv, flops, srcs[0], wp, u, sc, sh, out.t, out.t.shape[3], self.act_code(relu), rt)
+        elif S > 1:
+            # small-M launch (res_50 layer4 at B = 8: 256 blocks on 256 CUs): split-K, then the reduction + BN + activation
+            self.add_split("conv", conv, ".splitk", flops, S, self.B * Ho * Wo, wp.shape[0], lambda ones, zeros, ws: ops.conv2d_launch(
+                srcs, wp, ones, zeros, ws, kh=k, kw=k, stride=stride, pad=pad, cout=ws.shape[2], ksplit=S),
+                sc, sh, out.t, out.t.shape[3], self.act_code(relu))
+        else:
+            self.add("conv", conv, flops,
+                     ops.conv2d_launch(srcs, wp, sc, sh, out.t, kh=k, kw=k, stride=stride, pad=pad, cout=out.t.shape[3],
+                                       act=self.act_code(relu), res=rt, in_nchw=stem))
         return out
 
     def emit_conv_group(self, members):
         """Independent 3x3 / stride-1 convs (HRNet: the same conv of every parallel branch) as ONE F(2x4) launch when every member is
-        eligible (CP_GROUP=0: one launch each).  All outputs live in ONE pool slot: the launch record has a single output storage,
-        which is what `Engine.dependencies` tracks."""
+        eligible (CP_GROUP=0: one launch each); the outputs are `group_bufs` of one pool slot."""
         ok = self.winograd and os.environ.get("CP_GROUP", "1") != "0" and os.environ.get("CP_WINO24", "1") != "0" and 2 <= len(members) <= 4 and \
             all(ops.wino_eligible(x.t.shape[3], 3, 1, 1, 1) and not x.split for x, *_ in members)
         if not ok:
             return super().emit_conv_group(members)
-        sizes = [self.B * x.H * x.W * ops.round_up(co, 16) for x, _, _, co, _, _ in members]
-        slot = self.pool.take(sum(sizes))
-        holder = Act(1, 1, 1, slot)
-        weakref.finalize(holder, self.pool.give, slot)          # the slot returns to the pool when the last member activation is dropped
-        outs, recs, off, flops = [], [], 0, 0
-        for (x, conv, bn, co, relu, res), n in zip(members, sizes):
-            cp = ops.round_up(co, 16)
-            out = Act(x.H, x.W, co, slot[off:off + n].view(self.B, x.H, x.W, cp), parent=holder)
-            off += n
+        outs, whole = self.group_bufs([(x.H, x.W, co, ops.round_up(co, 16)) for x, _, _, co, _, _ in members])
+        recs, flops = [], 0
+        for (x, conv, bn, co, relu, res), out in zip(members, outs):
             wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
             sc, sh = ops.fold_bn(co, self.bn(bn), None, self.dev)
-            cin = x.t.shape[3]
-            ck = ("u24", conv, cin, co)
-            u24 = self.const_cache.get(ck)
-            if u24 is None:
-                u24 = self.const_cache[ck] = ops.pack_wino24_weight(wp, cin, co)
-            recs.append(dict(x=x.t, wp=wp, u24=u24, scale=sc, shift=sh, out=out.t, cout=cp, act=self.act_code(relu),
-                             res=res.t if res is not None else None))
+            recs.append(dict(x=x.t, wp=wp, u24=self.wino_weight("wino24", conv, wp, x.t.shape[3], co), scale=sc, shift=sh, out=out.t,
+                             cout=out.t.shape[3], act=self.act_code(relu), res=res.t if res is not None else None))
             flops += 2 * x.H * x.W * co * x.C * 9
-            outs.append(out)
-        self.add("wino24", "group:" + members[0][1], flops, ops.conv3x3_group_launch(recs, slot[:off]))
+        self.add("wino24", "group:" + members[0][1], flops, ops.conv3x3_group_launch(recs, whole))
         return outs
 
     def emit_conv_batch(self, members):
@@ -288,8 +274,8 @@ class PlanBuilder(nets.Graph):
         module's fuse paths, pose_higher_hrnet.py:169-212) as ONE grouped launch of the generic 64 x 64 implicit-GEMM tile per up to
         eight members (CP_GROUP=0 / CP_FUSE_GROUP=0: one launch each, with their own tile / split-K rules).  One by one these are
         13-29 us launches of 16-256 blocks on a 256-CU chip; weights / scale / shift are padded to 64 output rows for the shared tile
-        (zero rows: the padding channels of the output are written as zeros, as everywhere).  All outputs of a launch live in ONE
-        pool slot (`Engine.dependencies` tracks one output storage per launch record)."""
+        (zero rows: the padding channels of the output are written as zeros, as everywhere).  The outputs of a launch are
+        `group_bufs` of one pool slot."""
         ok = os.environ.get("CP_GROUP", "1") != "0" and os.environ.get("CP_FUSE_GROUP", "1") != "0" and len(members) >= 2 and \
             all(not x.split and x.t.shape[3] % 16 == 0 and not ops.wino_eligible(x.t.shape[3], k, stride, pad, 1) and not (k == 3 and x.t.shape[3] == 16)
                 for x, _, _, _, k, stride, pad, _ in members)
@@ -301,24 +287,18 @@ class PlanBuilder(nets.Graph):
             if len(chunk) == 1:
                 outs += super().emit_conv_batch(chunk)
                 continue
-            dims = [((x.H + 2 * pad - k) // stride + 1, (x.W + 2 * pad - k) // stride + 1) for x, _, _, _, k, stride, pad, _ in chunk]
-            sizes = [self.B * h * w * ops.round_up(m[3], 16) for (h, w), m in zip(dims, chunk)]
-            slot = self.pool.take(sum(sizes))
-            holder = Act(1, 1, 1, slot)
-            weakref.finalize(holder, self.pool.give, slot)      # the slot returns to the pool when the last member activation is dropped
-            recs, off, flops = [], 0, 0
-            for (x, conv, bn, co, k, stride, pad, relu), (h, w), n in zip(chunk, dims, sizes):
-                cp = ops.round_up(co, 16)
-                out = Act(h, w, co, slot[off:off + n].view(self.B, h, w, cp), parent=holder)
-                off += n
+            couts, whole = self.group_bufs([((x.H + 2 * pad - k) // stride + 1, (x.W + 2 * pad - k) // stride + 1, co, ops.round_up(co, 16))
+                                            for x, _, _, co, k, stride, pad, _ in chunk])
+            recs, flops = [], 0
+            for (x, conv, bn, co, k, stride, pad, relu), out in zip(chunk, couts):
                 wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
                 sc, sh = ops.fold_bn(co, self.bn(bn), None, self.dev)
                 ldw = ops.round_up(wp.shape[0], 64)
-                recs.append(dict(x=x.t, wp=ops.pad_rows(wp, ldw), scale=ops.pad_vec(sc, ldw), shift=ops.pad_vec(sh, ldw), out=out.t, cout=cp,
-                                 k=k, stride=stride, pad=pad, act=self.act_code(relu)))
-                flops += 2 * h * w * co * x.C * k * k
-                outs.append(out)
-            self.add("conv", "group:" + chunk[0][1], flops, ops.conv2d_group_launch(recs, slot[:off]))
+                recs.append(dict(x=x.t, wp=ops.pad_rows(wp, ldw), scale=ops.pad_vec(sc, ldw), shift=ops.pad_vec(sh, ldw), out=out.t,
+                                 cout=out.t.shape[3], k=k, stride=stride, pad=pad, act=self.act_code(relu)))
+                flops += 2 * out.H * out.W * co * x.C * k * k
+            self.add("conv", "group:" + chunk[0][1], flops, ops.conv2d_group_launch(recs, whole))
+            outs += couts
         return outs
 
     def emit_maxpool(self, x, k, s, p):
@@ -342,27 +322,17 @@ class PlanBuilder(nets.Graph):
         out = self.buf(x.H, x.W, co)
         wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
         sc, sh = ops.fold_bn(co, self.bn(bn), self.w(conv + ".bias"), self.dev)
-        uom = self.wino(wom, x.t.shape[3], 32, key=conv + ".conv_offset_mask", hw=(x.H, x.W))
-        if uom is not None:
-            self.add_wino(conv + ".conv_offset_mask", 2 * x.H * x.W * 27 * x.C * 9, x.t, wom, uom, som, hom, om.t, 32, ops.ACT_NONE)
-        else:
-            self.add("conv", conv + ".conv_offset_mask", 2 * x.H * x.W * 27 * x.C * 9,
-                     ops.conv2d_launch([x.t], wom, som, hom, om.t, kh=3, kw=3, stride=1, pad=1, cout=32))
+        uom = self.wino(wom, x.t.shape[3], 32, conv + ".conv_offset_mask", hw=(x.H, x.W))
+        self.add_conv3x3(conv + ".conv_offset_mask", 2 * x.H * x.W * 27 * x.C * 9, x.t, wom, uom, som, hom, om.t, 32, ops.ACT_NONE)
         flops = 2 * x.H * x.W * co * x.C * 9
         S = ops.dcn_ksplit(ops.rule_batch(self.B) * x.H * x.W, wp.shape[0]) if self.dcn_splitk else 1
         if S > 1:
-            # small-M layer (512 -> 256 @16x16 at B = 16 is 256 blocks of 288 k-steps on 256 CUs): split-K over the taps into a
-            # workspace of raw partial sums, then a fixed-order reduction + BN + ReLU (deterministic; two launches)
-            ldw = wp.shape[0]
-            ws = self.pool.take(S * self.B * x.H * x.W * ldw)
-            wst = ws[: S * self.B * x.H * x.W * ldw].view(S, self.B * x.H * x.W, ldw)
-            ones, zeros = self.unit_scale(ldw)
-            self.add("dcn", conv, flops, ops.dcn_v2_launch(x.t, om.t, wp, ones, zeros, wst, cout=ldw, om_sigmoid=True, ksplit=S))
-            self.add("sum", conv + ".splitk", 0, ops.splitk_reduce_launch(wst, sc, sh, out.t, cout=out.t.shape[3], act=ops.ACT_RELU))
-            self.pool.give(ws)
-            return out
-        self.add("dcn", conv, flops,
-                 ops.dcn_v2_launch(x.t, om.t, wp, sc, sh, out.t, cout=out.t.shape[3], om_sigmoid=True, act=ops.ACT_RELU))
+            # small-M layer (512 -> 256 @16x16 at B = 16 is 256 blocks of 288 k-steps on 256 CUs): split-K over the taps, then BN + ReLU
+            self.add_split("dcn", conv, ".splitk", flops, S, self.B * x.H * x.W, wp.shape[0], lambda ones, zeros, ws: ops.dcn_v2_launch(
+                x.t, om.t, wp, ones, zeros, ws, cout=ws.shape[2], om_sigmoid=True, ksplit=S), sc, sh, out.t, out.t.shape[3], ops.ACT_RELU)
+        else:
+            self.add("dcn", conv, flops,
+                     ops.dcn_v2_launch(x.t, om.t, wp, sc, sh, out.t, cout=out.t.shape[3], om_sigmoid=True, act=ops.ACT_RELU))
         return out
 
     def emit_up_add(self, x, wname, f, add):
@@ -431,23 +401,15 @@ class PlanBuilder(nets.Graph):
 
     def emit_sum_up_batch(self, members, relu):
         """The per-branch sums that end an HRNet module as ONE launch (CP_GROUP=0 / CP_SUM_GROUP=0: one launch each).  Launched one by
-        one they are 7-12 us for 10-39 MB each and sit on the critical path between two modules; all outputs of the launch live in ONE
-        pool slot (`Engine.dependencies` tracks one output storage per launch record).  Bit-identical to the single launches."""
+        one they are 7-12 us for 10-39 MB each and sit on the critical path between two modules; the outputs are `group_bufs` of one
+        pool slot.  Bit-identical to the single launches."""
         ok = os.environ.get("CP_GROUP", "1") != "0" and os.environ.get("CP_SUM_GROUP", "1") != "0" and 2 <= len(members) <= 4 and \
             all(len(xs) <= 4 and not any(a.split for a in xs) for xs, _ in members)
         if not ok:
             return super().emit_sum_up_batch(members, relu)
-        sizes = [self.B * xs[0].H * xs[0].W * xs[0].t.shape[3] for xs, _ in members]
-        slot = self.pool.take(sum(sizes))
-        holder = Act(1, 1, 1, slot)
-        weakref.finalize(holder, self.pool.give, slot)          # the slot returns to the pool when the last member activation is dropped
-        outs, recs, off = [], [], 0
-        for (xs, shifts), n in zip(members, sizes):
-            out = Act(xs[0].H, xs[0].W, xs[0].C, slot[off:off + n].view(self.B, xs[0].H, xs[0].W, xs[0].t.shape[3]), parent=holder)
-            off += n
-            recs.append(([a.t for a in xs], shifts, out.t))
-            outs.append(out)
-        self.add("sum", "group:fuse", 0, ops.sum_up_group_launch(recs, slot[:off], relu))
+        outs, whole = self.group_bufs([(xs[0].H, xs[0].W, xs[0].C, xs[0].t.shape[3]) for xs, _ in members])
+        recs = [([a.t for a in xs], shifts, out.t) for (xs, shifts), out in zip(members, outs)]
+        self.add("sum", "group:fuse", 0, ops.sum_up_group_launch(recs, whole, relu))
         return outs
 
     def emit_head(self, feat, p, hc):
@@ -462,17 +424,12 @@ class PlanBuilder(nets.Graph):
         per_head = ops.rule_batch(self.B) * H * W * hc * 4 <= 300 * (1 << 20) and hc >= 64
         ft = feat.t
         outs = []
-        if per_head:
-            mid = self.buf(H, W, hc)
-        else:
-            mid = self.buf(H, W, 6 * hc)
-            w3 = self.expand_in(torch.cat([self.w("%s.%s.0.weight" % (p, h)) for h, _ in nets.HEADS], 0), [feat])
-            b3 = torch.cat([self.w("%s.%s.0.bias" % (p, h)) for h, _ in nets.HEADS], 0)
-            wp3 = ops.pack_conv_weight(w3)
-            sc3, sh3 = ops.fold_bn(6 * hc, None, b3, self.dev)
-            u3 = self.wino(wp3, feat.t.shape[3], 6 * hc, key=p + ".*.0")
-            self.add("wino" if u3 is not None else "conv", p + ".*.0", 2 * H * W * 6 * hc * feat.C * 9,
-                     ops.conv2d_launch([ft], wp3, sc3, sh3, mid.t, kh=3, kw=3, stride=1, pad=1, cout=6 * hc, act=ops.ACT_RELU, wino=u3))
+        mid = self.buf(H, W, hc if per_head else 6 * hc)
+        if not per_head:
+            wp3 = ops.pack_conv_weight(self.expand_in(torch.cat([self.w("%s.%s.0.weight" % (p, h)) for h, _ in nets.HEADS], 0), [feat]))
+            sc3, sh3 = ops.fold_bn(6 * hc, None, torch.cat([self.w("%s.%s.0.bias" % (p, h)) for h, _ in nets.HEADS], 0), self.dev)
+            self.add_conv3x3(p + ".*.0", 2 * H * W * 6 * hc * feat.C * 9, ft, wp3, self.wino(wp3, ft.shape[3], 6 * hc, p + ".*.0"), sc3, sh3,
+                             mid.t, 6 * hc, ops.ACT_RELU, splitc=False)
         for i, (h, n) in enumerate(nets.HEADS):
             if self.dets_only and h in SPARSE_HEADS:
                 outs.append(None)
@@ -482,33 +439,24 @@ class PlanBuilder(nets.Graph):
             sc, sh = ops.fold_bn(n, None, self.w("%s.%s.2.bias" % (p, h)), self.dev)
             act = ops.ACT_SIGMOID if h in self.sigmoid_heads else ops.ACT_NONE
             if per_head:
-                wp3h = ops.pack_conv_weight(self.expand_in(self.w("%s.%s.0.weight" % (p, h)), [feat]))
-                sc3h, sh3h = ops.fold_bn(hc, None, self.w("%s.%s.0.bias" % (p, h)), self.dev)
+                key = "%s.%s.0" % (p, h)
+                wp3h = ops.pack_conv_weight(self.expand_in(self.w(key + ".weight"), [feat]))
+                sc3h, sh3h = ops.fold_bn(hc, None, self.w(key + ".bias"), self.dev)
                 fused_ok = self.fuse_heads and ops.head3x3_1x1_eligible(ft, hc, n)
-                # the fused launch is an F(2x2) kernel; a head that runs as two launches may take the F(2x4) kernel (res_50: 256 -> 64)
-                u3h = self.wino(wp3h, feat.t.shape[3], hc, key="%s.%s.0" % (p, h), hw=None if fused_ok else (H, W))
+                # the fused launch picks its own transform below; a head that runs as two launches may take the F(2x4) kernel (res_50: 256 -> 64)
+                u3h = self.wino(wp3h, ft.shape[3], hc, key, hw=None if fused_ok else (H, W))
                 if u3h is not None and fused_ok:
-                    h24 = ops.head_wino24_wanted(ft, n)
-                    if h24:            # F(2x4) head kernel: its own weight transform
-                        ck = ("u24", "%s.%s.0" % (p, h), feat.t.shape[3], hc)
-                        u3h = self.const_cache.get(ck)
-                        if u3h is None:
-                            u3h = self.const_cache[ck] = ops.pack_wino24_weight(wp3h, feat.t.shape[3], hc)
+                    if ops.head_wino24_wanted(ft, n):            # F(2x4) head kernel: its own weight transform
+                        u3h = "wino24", self.wino_weight("wino24", key, wp3h, ft.shape[3], hc)
                     # the 1x1 rides in the Winograd kernel (<= 2 outputs: epilogue registers; hps / hm_hp: a second MFMA phase
                     # over the LDS-resident tile): the [B,H,W,hc] intermediate (268 MB at B = 16) is neither written nor read back
                     w2 = self.w("%s.%s.2.weight" % (p, h)).reshape(n, hc).contiguous()
-                    self.add("wino24" if h24 else "wino", "%s.%s.0+2" % (p, h), 2 * H * W * (hc * feat.C * 9 + n * hc),
-                             ops.head3x3_1x1_launch(ft, u3h, sc3h, sh3h, w2, self.w("%s.%s.2.bias" % (p, h)), o, hc=hc, act2=act, wino24=h24))
+                    self.add(u3h[0], key + "+2", 2 * H * W * (hc * feat.C * 9 + n * hc),
+                             ops.head3x3_1x1_launch(ft, u3h[1], sc3h, sh3h, w2, self.w("%s.%s.2.bias" % (p, h)), o, hc=hc, act2=act,
+                                                    wino24=u3h[0] == "wino24"))
                     outs.append(o)
                     continue
-                if isinstance(u3h, tuple):
-                    self.add("wino24", "%s.%s.0" % (p, h), 2 * H * W * hc * feat.C * 9,
-                             ops.conv2d_launch([ft], wp3h, sc3h, sh3h, mid.t, kh=3, kw=3, stride=1, pad=1, cout=hc, act=ops.ACT_RELU,
-                                               wino=u3h[1], tile=ops.WINO24))
-                else:
-                    self.add("wino" if u3h is not None else "conv", "%s.%s.0" % (p, h), 2 * H * W * hc * feat.C * 9,
-                             ops.conv2d_launch([ft], wp3h, sc3h, sh3h, mid.t, kh=3, kw=3, stride=1, pad=1, cout=hc, act=ops.ACT_RELU,
-                                               wino=u3h))
+                self.add_conv3x3(key, 2 * H * W * hc * feat.C * 9, ft, wp3h, u3h, sc3h, sh3h, mid.t, hc, ops.ACT_RELU, splitc=False)
                 sl = mid.t
             else:
                 sl = mid.t[..., i * hc:(i + 1) * hc]

@@ -36,7 +36,7 @@ class Launch:
     """One enqueue of a C-ABI kernel entry point with everything resolved at plan time: the C function, its descriptor
     struct (or None), the tensor arguments in C order (None = NULL) and the integer arguments.  `run()` only passes
     cached device pointers and the current stream.  The same record is what `plan.py` serialises and what the C plan
-    runtime (csrc/plan_runtime.cpp, `cp_plan_*`) replays -- `FN_SIGNATURES` is the contract between the three."""
+    runtime (csrc/plan_runtime.cpp, `cp_plan_*`) replays -- `marshal` below and `run_op` there are the contract between the three."""
     __slots__ = ("fn", "desc", "tensors", "ints", "out_index", "kernel", "_cfn", "_args")
 
     def __init__(self, fn, desc, tensors, ints=(), out_index=-1):
