@@ -44,13 +44,15 @@ int cp_decode_assign_f32(const float*, const float*, const float*, const float*,
 int cp_head_points_f32(const float*, int, const int*, const float*, const float*, const float*, const float*, float*, int, int, int, int, int,
                        int, int, void*);
 int cp_flip_merge_pairs_f32(int, const float* const*, float* const*, const int*, int, int, int, int, const int*, void*);
+int cp_head_points_pairs_f32(const float*, int, const int*, const int*, const float*, const float*, const float*, const float*, float*, int, int,
+                             int, int, int, int, int, void*);
 }
 
 namespace {
 
 enum { FN_CONV = 1, FN_WINO = 2, FN_DCN = 3, FN_STEM7 = 4, FN_POOL = 5, FN_UPADD = 6, FN_SUMUP = 7, FN_DWCONV = 8, FN_AVGPOOL = 9,
        FN_SCALEADD = 10, FN_SHUFFLE = 11, FN_HEAD = 12, FN_TOPK = 13, FN_ASSIGN = 14, FN_SPLITK = 15, FN_WINO24G = 16, FN_CONVG = 17, FN_SUMUPG = 18,
-       FN_POINTS = 19, FN_FLIPPAIRS = 20 };   // ops.FN_IDS
+       FN_POINTS = 19, FN_FLIPPAIRS = 20, FN_POINTSPAIRS = 21 };   // ops.FN_IDS
 enum { REF_NULL = 0, REF_BUF = 1, REF_CONST = 2 };
 
 struct Op {
@@ -165,6 +167,9 @@ int run_op(const Op& o, hipStream_t s)
         case FN_FLIPPAIRS:    // ptrs: in x4, out x4, perm, (the storage all outputs live in); ints: n, N, H, W, J, (C, mode) x4
             return cp_flip_merge_pairs_f32(I[0], reinterpret_cast<const float* const*>(P.data()), reinterpret_cast<float* const*>(P.data() + 4), I + 5,
                                            I[1], I[2], I[3], I[4], reinterpret_cast<const int*>(P[8]), s);
+        case FN_POINTSPAIRS:  // ptrs: feat, ws_inds, perm, w1, b1, w2, b2, out (the four merged sparse maps); ints: featLd, N, H, W, C, J, K, hc
+            return cp_head_points_pairs_f32(P[0], I[0], reinterpret_cast<const int*>(P[1]), reinterpret_cast<const int*>(P[2]), P[3], P[4], P[5],
+                                            P[6], P[7], I[1], I[2], I[3], I[4], I[5], I[6], I[7], s);
     }
     cp_set_error("plan: unknown launch function %u", o.fn);
     return 1;
@@ -194,6 +199,7 @@ bool arity_ok(const Op& o)
         case FN_ASSIGN: return o.ptrs.size() == 7 && o.ints.size() == 5;
         case FN_POINTS: return o.ptrs.size() == 7 && o.ints.size() == 8;
         case FN_FLIPPAIRS: return o.ptrs.size() == 10 && o.ints.size() == 13 && o.ints[0] >= 1 && o.ints[0] <= 4;
+        case FN_POINTSPAIRS: return o.ptrs.size() == 8 && o.ints.size() == 8;
     }
     return false;
 }
@@ -419,12 +425,13 @@ extern "C" int cp_plan_info(const cp_plan* pl, int* B, int* H, int* W, int* n_ou
 extern "C" float* cp_plan_input(const cp_plan* pl) { return pl ? pl->input : nullptr; }
 
 // A detections-only plan (Engine(..., dets_only=True)) evaluates wh / hps / reg / hp_offset only at the decoded peaks: the launch that
-// does so is what identifies it (no header field: plan files of every earlier writer keep loading unchanged).
+// does so is what identifies it (no header field: plan files of every earlier writer keep loading unchanged).  Under the flip test
+// (Engine(..., flip_dets_only=True)) that launch is the pairs form, and cp_plan_flip_test says 1 as well.
 extern "C" int cp_plan_dets_only(const cp_plan* pl)
 {
     if (!pl) return -1;
     for (const Op& o : pl->ops)
-        if (o.fn == FN_POINTS) return 1;
+        if (o.fn == FN_POINTS || o.fn == FN_POINTSPAIRS) return 1;
     return 0;
 }
 

@@ -345,19 +345,24 @@ class BaseDetector(object):
     def _process_batch(self, images):
         raise NotImplementedError
 
+    def process_dets(self, images):
+        raise NotImplementedError
+
     def post_process_batch(self, dets, metas, scale=1):
         raise NotImplementedError
 
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images):
+    def run_batch(self, images, dets_only=False):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
         launch per group (soft-NMS on the device when TEST.NMS or several scales); ONE download.  The download is the only
         synchronisation, so there are no stage timers: run() is the timed form.  With FLIP_TEST and a head gated off by cfg.LOSS
-        `process` takes one pair at a time; the stages around it stay batched."""
+        `process` takes one pair at a time; the stages around it stay batched.
+        dets_only=True: every group goes through `process_dets` (a detections-only plan, under FLIP_TEST too) instead of `process`;
+        ValueError where `process_dets` raises it."""
         images = self._check_batch(images)
         if not images:
             return []
@@ -379,7 +384,7 @@ class BaseDetector(object):
                 j = g * len(self.scales) + k
                 table, scratch_bytes, inp_h, inp_w = work[j]
                 x = self._launch_pre(staging, parts[2 * j], table, scratch_bytes, inp_h, inp_w)
-                dets = self._process_batch(x)
+                dets = self.process_dets(x) if dets_only else self._process_batch(x)
                 per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
             merged.append(self.merge_outputs_batch(per_scale))
         rows = (merged[0] if len(merged) == 1 else torch.cat(merged, 0)).cpu().numpy()          # the one download
@@ -455,7 +460,8 @@ class MultiPoseDetector(BaseDetector):
         if return_time:
             return "dets_only=True cannot time 'net' / 'dec' separately (return_time=True)"
         if self.cfg.TEST.FLIP_TEST:
-            return "dets_only=True does not support TEST.FLIP_TEST (the flip merge needs the dense maps)"
+            return ("dets_only=True does not support TEST.FLIP_TEST here (this call hands out head maps, and the flip merge needs the "
+                    "dense ones): use process_dets(images) or run_batch(images, dets_only=True)")
         if not (loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS):
             return "dets_only=True needs every head enabled by cfg.LOSS (REG_OFFSET, HM_HP, REG_HP_OFFSET, no MSE_LOSS)"
         if not self._one_replay_path():
@@ -537,6 +543,26 @@ class MultiPoseDetector(BaseDetector):
         if return_time:
             return outputs, dets, forward_time
         return outputs, dets
+
+    def process_dets(self, images):
+        """Detections and nothing else, the way the config says: images as for `process` -> dets (fresh tensor).
+        FLIP_TEST on: N = B / 2 image / mirrored-twin pairs (image n at 2n, twin at 2n + 1) through the detections-only flip-test plan
+        (model.process(..., flip_dets_only=True)): hm / hm_hp dense and merged as always, wh / hps / reg / hp_offset evaluated and
+        merged only at the peaks of the merged heat maps -> [N, K, 56].  FLIP_TEST off: `process(images, dets_only=True)[1]`,
+        [B, K, 56].  A head gated off by cfg.LOSS raises ValueError (there is no silent fall-back to a dense plan)."""
+        loss = self.cfg.LOSS
+        if not (loss.REG_OFFSET and loss.HM_HP and loss.REG_HP_OFFSET and not loss.MSE_LOSS):
+            raise ValueError("process_dets needs every head enabled by cfg.LOSS (REG_OFFSET, HM_HP, REG_HP_OFFSET, no MSE_LOSS)")
+        if not hasattr(self.model, "process"):
+            raise ValueError("process_dets needs a model with the one-replay process()")
+        extra = {"dets_only": True}
+        if self.cfg.TEST.FLIP_TEST:
+            B = images.shape[0]
+            if B < 2 or B % 2:
+                raise ValueError("FLIP_TEST needs image / mirrored-twin pairs: an even batch [img0, twin0, img1, twin1, ...], got %d" % B)
+            extra = {"flip_dets_only": True}
+        with torch.no_grad():
+            return self.model.process(images, self.cfg.TEST.TOPK, **extra)[1]
 
     def post_process(self, dets, meta, scale=1):
         """multi_pose.py:62-71 (batch-1 by construction, like the reference): feature-map pixels -> image pixels / scale,

@@ -534,7 +534,16 @@ class Engine:
 
     def __init__(self, arch, state_dict, batch, height=512, width=512, device="cuda", head_conv=None,
                  sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None, dets_only=False,
-                 flip_test=False):
+                 flip_test=False, flip_dets_only=False):
+        if flip_dets_only:
+            # detections-only under the flip test: its own keyword (flip_test=True with dets_only=True keeps refusing below)
+            if flip_test or dets_only:
+                raise ValueError("flip_dets_only=True is a mode of its own: it does not combine with flip_test=True or dets_only=True")
+            if batch % 2:
+                raise ValueError("flip_dets_only=True needs image / mirrored-twin pairs: an even batch [img0, twin0, img1, twin1, ...], "
+                                 "got %d" % batch)
+            if not decode_k:
+                raise ValueError("flip_dets_only=True needs decode_k: the sparse heads are evaluated at the peaks of the plan's own decode")
         if dets_only and not decode_k:
             raise ValueError("dets_only=True needs decode_k: the sparse heads are evaluated at the peaks of the plan's own decode")
         if flip_test:
@@ -561,14 +570,14 @@ class Engine:
                 raise ValueError("parameter %s has shape %s, expected %s" % (k, tuple(sd[k].shape), shp))
         with torch.cuda.device(self.device):
             self.input = torch.zeros((batch, 3, height, width), dtype=torch.float32, device=self.device)
-            pb = PlanBuilder(sd, batch, self.device, sigmoid_heads, const_cache, dets_only=bool(dets_only))
+            pb = PlanBuilder(sd, batch, self.device, sigmoid_heads, const_cache, dets_only=bool(dets_only or flip_dets_only))
             pb.network(self.arch, Act(height, width, 3, self.input), head_conv)
         self.launches = pb.launches
         self.emission = pb.launches    # the list in the order of the reference's forward(); `launches` may later be re-ordered by the schedule
         self.outputs = pb.outputs      # what forward() returns: [hm, None, None, None, hm_hp, None] for a detections-only plan
         self.head_maps = pb.outputs    # the six map storages (a detections-only plan: the sparse ones too; what a plan file lists)
-        self.dets_only = bool(dets_only)
-        self.flip_test = bool(flip_test)
+        self.dets_only = bool(dets_only or flip_dets_only)
+        self.flip_test = bool(flip_test or flip_dets_only)
         self._points = pb.points
         self.flops_per_image = pb.flops
         self.activation_bytes = pb.bytes_alloc
@@ -593,7 +602,9 @@ class Engine:
         if self.flip_test:
             # multi_pose.py:45-53 for N = B / 2 pairs inside the schedule: two merge launches, each into ONE storage, and the decode
             # of the N merged maps.  The peak merge (hm, hm_hp) feeds the peak extraction and may run beside the remaining heads.
-            hm, wh, hps, reg, hm_hp, hp_offset, merges = self._flip_merges(J)
+            # Detections-only (flip_dets_only): the peak merge alone; the other four merged maps exist only at the decoded peaks, where
+            # the pairs points launch below evaluates and merges them.
+            hm, wh, hps, reg, hm_hp, hp_offset, merges, permt = self._flip_merges(J, regress=not self.dets_only)
             B = B // 2
         with torch.cuda.device(self.device):
             ws = torch.zeros((2, B, 1 + J, K), dtype=torch.float32, device=self.device)
@@ -606,24 +617,33 @@ class Engine:
                     views.append(sparse[off:off + B * n * H * W].view(B, n, H, W))
                     off += B * n * H * W
                 wh, hps, reg, hp_offset = views
-                self.head_maps = [hm, wh, hps, reg, hm_hp, hp_offset]
+                # (under the flip test hm / hm_hp stay the un-merged [2N] outputs, as in every flip-test plan; the sparse four are [N])
+                self.head_maps = [self.outputs[0], wh, hps, reg, self.outputs[4], hp_offset]
                 self.activation_bytes += 4 * sparse.numel()
         topk, assign = ops.decode_launches(hm, wh, hps, reg, hm_hp, hp_offset, K, ws, self.dets)
         tail = merges[:1] + [("decode", DECODE_TOPK, 0, topk)] + merges[1:]
         if self.dets_only:
             pt = self._points
             hc, C = pt["hc"], pt["feat"].C
-            points = ops.head_points_launch(pt["feat"].t, ws[1], pt["w1"], pt["b1"], pt["w2"], pt["b2"], sparse, hc=hc, J=J, K=K)
             # algorithmic flops per image: 3 branches at K centres + hp_offset at J*K joint peaks
             flops = K * 2 * (3 * hc * C * 9 + (4 + 2 * J) * hc) + J * K * 2 * (hc * C * 9 + 2 * hc)
-            tail.append(("points", "head_points", flops * B, points))
+            if self.flip_test:
+                points = ops.head_points_pairs_launch(pt["feat"].t, ws[1], permt, pt["w1"], pt["b1"], pt["w2"], pt["b2"], sparse, hc=hc,
+                                                      J=J, K=K)
+                # per pair: the above on the image, plus wh and hps on the twin at the K centres
+                flops += K * 2 * (2 * hc * C * 9 + (2 + 2 * J) * hc)
+                tail.append(("points", "head_points_pairs", flops * B, points))
+            else:
+                points = ops.head_points_launch(pt["feat"].t, ws[1], pt["w1"], pt["b1"], pt["w2"], pt["b2"], sparse, hc=hc, J=J, K=K)
+                tail.append(("points", "head_points", flops * B, points))
         tail.append(("decode", "decode.pose_assign", 0, assign))
         self.launches = self.emission = self.launches + tail
         self.activation_bytes += 4 * (ws.numel() + self.dets.numel())
         self.decode_k = K
 
-    def _flip_merges(self, J):
-        """The merged maps of a flip-test plan and their two launches: -> (hm, wh, hps, reg, hm_hp, hp_offset as [N] views, launches)."""
+    def _flip_merges(self, J, regress=True):
+        """The merged maps of a flip-test plan and their two launches: -> (hm, wh, hps, reg, hm_hp, hp_offset as [N] views, launches,
+        the device joint permutation).  regress=False: the peak merge only (wh / hps / reg / hp_offset come back as None)."""
         if J != 17:
             raise ValueError("flip_test=True swaps the 17 COCO joints (FLIP_IDX); this plan has %d" % J)
         perm = list(range(J))
@@ -632,6 +652,8 @@ class Engine:
         modes = ops.FLIP_MODES
         groups = (((0, modes["flip"]), (4, modes["joints"])),
                   ((1, modes["flip"]), (2, modes["offsets"]), (3, modes["copy"]), (5, modes["copy"])))
+        if not regress:
+            groups = groups[:1]
         merged = [None] * 6
         launches = []
         with torch.cuda.device(self.device):
@@ -648,7 +670,7 @@ class Engine:
                     off += n
                 self.activation_bytes += 4 * whole.numel()
                 launches.append(("flip", FLIP_PEAKS if gi == 0 else "flip.merge_regress", 0, ops.flip_pairs_launch(maps, whole, permt)))
-        return tuple(merged) + (launches,)
+        return tuple(merged) + (launches, permt)
 
     def process(self, images):
         """forward + decode in one replay (engines built with `decode_k`): -> (the six heads, dets [B, K, 5+3J]); static

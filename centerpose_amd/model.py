@@ -52,9 +52,10 @@ class BackBoneWithHead:
     def eval(self):
         return self
 
-    def engine_for(self, B, H, W, decode_k=None, dets_only=False, flip_test=False):
+    def engine_for(self, B, H, W, decode_k=None, dets_only=False, flip_test=False, flip_dets_only=False):
         """The compiled plan for (B, H, W) [with the decode inside its schedule: decode_k] [detections-only: dets_only, see
-        `process`] [B / 2 image / mirrored-twin pairs merged inside the plan: flip_test], cached per that whole key."""
+        `process`] [B / 2 image / mirrored-twin pairs merged inside the plan: flip_test] [both at once: flip_dets_only], cached per
+        that whole key."""
         key = (B, H, W) if decode_k is None else (B, H, W, int(decode_k))
         if dets_only:
             key += ("dets_only",)
@@ -62,6 +63,11 @@ class BackBoneWithHead:
         if flip_test:
             key += ("flip",)
             extra["flip_test"] = True
+        if flip_dets_only:
+            # (a key of its own, and not one `forward` looks for: this plan has four of the six maps at the peaks only, so unlike a
+            # flip_test plan it does not stand in for the forward-only plan of its shape)
+            key += ("flip_dets_only",)
+            extra["flip_dets_only"] = True
         eng = self._engines.get(key)
         if eng is not None:
             self._engines.move_to_end(key)
@@ -94,7 +100,7 @@ class BackBoneWithHead:
 
     __call__ = forward
 
-    def process(self, x, K=100, dets_only=False, flip_test=False):
+    def process(self, x, K=100, dets_only=False, flip_test=False, flip_dets_only=False):
         """forward + multi_pose_decode as ONE hipGraph replay (engine built with the decode inside its schedule):
         -> ([hm, wh, hps, reg, hm_hp, hp_offset], dets [B, K, 56]).
         dets_only=True: a detections-only plan -- hm / hm_hp dense as always (same launches, same bits), the wh / hps / reg
@@ -106,10 +112,15 @@ class BackBoneWithHead:
         reference returns them, dets [N, K, 56]).  `dets` is a FRESH tensor owned by the caller, like the
         reference's (decode.py:305-307 returns a torch.cat result): a stream-ordered copy of the plan's static buffer
         (22.4 KB per image), so collecting dets over several calls or handing them to `dist.DetsGatherer.submit` is safe.
+        flip_dets_only=True: both at once -- x as for flip_test; hm / hm_hp dense for the 2N images and merged as always, the other four
+        branches evaluated and merged only at the peaks of the merged heat maps (cp_head_points_pairs_f32) ->
+        ([hm, None, None, None, hm_hp, None] at batch B, dets [N, K, 56]).
         The six head maps are the plan's static output buffers (3.8 MB per image), overwritten by the next call -- the same
         contract as `forward`."""
         B, _, H, W = x.shape
         extra = {"flip_test": True} if flip_test else {}      # the default calls stay exactly what they were
+        if flip_dets_only:
+            extra["flip_dets_only"] = True
         outs, dets = self.engine_for(B, H, W, decode_k=K, dets_only=dets_only, **extra).process(x)
         return outs, dets.clone()
 

@@ -119,6 +119,8 @@ def marshal(fn, desc, ptrs, ints):
         return ptrs[:6] + ints + [ptrs[6]]
     if fn == "cp_head_points_f32":                # ptrs: feat, ws_inds, w1, b1, w2, b2, out; ints: featLd, B, H, W, C, J, K, hc
         return [ptrs[0], ints[0]] + ptrs[1:] + ints[1:]
+    if fn == "cp_head_points_pairs_f32":          # ptrs: feat, ws_inds, perm, w1, b1, w2, b2, out; ints: featLd, N, H, W, C, J, K, hc
+        return [ptrs[0], ints[0]] + ptrs[1:] + ints[1:]
     if fn == "cp_flip_merge_pairs_f32":           # ptrs: in x4, out x4, perm, whole; ints: n, N, H, W, J, (C, mode) x4
         ins = (ctypes.c_void_p * 4)(*[p.value for p in ptrs[:4]])
         outs = (ctypes.c_void_p * 4)(*[p.value for p in ptrs[4:8]])
@@ -132,7 +134,7 @@ FN_IDS = {"cp_conv2d_f32": 1, "cp_conv3x3_winograd_f32": 2, "cp_dcn_v2_f32": 3, 
           "cp_global_avgpool_nhwc_f32": 9, "cp_scale_add_nhwc_f32": 10, "cp_shuffle_concat_nhwc_f32": 11, "cp_head3x3_1x1_f32": 12,
           "cp_decode_topk_f32": 13, "cp_decode_assign_f32": 14, "cp_splitk_reduce_f32": 15, "cp_conv3x3_winograd24_group_f32": 16, "cp_conv2d_group_f32": 17,
           "cp_sum_up_group_nhwc_f32": 18, "cp_head_points_f32": 19,
-          "cp_flip_merge_pairs_f32": 20}
+          "cp_flip_merge_pairs_f32": 20, "cp_head_points_pairs_f32": 21}
 
 
 def pad_rows(t, ldw):
@@ -748,6 +750,21 @@ def head_points_launch(feat, inds, w1, b1, w2, b2, out, *, hc, J, K):
     for t in (w1, b1, w2, b2):
         assert t.is_contiguous() and t.dtype == torch.float32
     return Launch("cp_head_points_f32", None, [feat, inds, w1, b1, w2, b2, out], [_ld(feat), B, H, W, C, J, K, hc], out_index=6)
+
+
+def head_points_pairs_launch(feat, inds, perm, w1, b1, w2, b2, out, *, hc, J, K):
+    """`head_points_launch` under the flip test (cp_head_points_pairs_f32) as one launch record.  feat: the head input NHWC
+    [2N,H,W,C physical] with image n at 2n and its mirrored twin at 2n + 1; inds: the peak extraction's [N,1+J,K] on the N MERGED
+    heat maps; perm: the joint permutation of `flip_pairs_launch` (int32 bits in a float32 tensor [J]); the four constants exactly as
+    for `head_points_launch`; out: ONE storage of N*H*W*(6+2J) floats that holds the four MERGED NCHW maps back to back."""
+    N2, H, W, C = feat.shape
+    N = N2 // 2
+    assert N2 % 2 == 0 and perm.dtype == torch.float32 and perm.is_contiguous() and perm.numel() == J
+    assert tuple(inds.shape) == (N, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == N * H * W * (6 + 2 * J)
+    assert w1.numel() == 4 * 9 * C * hc and b1.numel() == 4 * hc and tuple(w2.shape) == (6 + 2 * J, hc) and b2.numel() == 6 + 2 * J
+    for t in (w1, b1, w2, b2):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    return Launch("cp_head_points_pairs_f32", None, [feat, inds, perm, w1, b1, w2, b2, out], [_ld(feat), N, H, W, C, J, K, hc], out_index=7)
 
 
 FLIP_MODES = {"flip": 0, "joints": 1, "offsets": 2, "copy": 3}     # cp_flip_merge_pairs_f32 modes (hm / wh, hm_hp, hps, reg / hp_offset)

@@ -255,6 +255,16 @@ int cp_decode_assign_f32(const float* wh, const float* kps, const float* reg, co
  * values depend only on its 3x3 patch (duplicates are written with identical bits).  hc % 32 == 0, hc <= 512, C <= 512. */
 int cp_head_points_f32(const float* feat, int featLd, const int* ws_inds, const float* w1, const float* b1, const float* w2,
                        const float* b2, float* out, int B, int H, int W, int C, int J, int K, int hc, void* stream);
+/* The same four branches under the flip test (multi_pose.py:45-53), at the peaks of the N MERGED heat maps.  feat: the head input of
+ * the 2N images, pairs interleaved (image n at batch 2n, its mirrored twin at 2n + 1); ws_inds: cp_decode_topk_f32's [N,1+J,K] on
+ * the merged hm / hm_hp; perm: the DEVICE joint permutation int[J] of cp_flip_merge_pairs_f32; w1 / b1 / w2 / b2: exactly as above.
+ * out: the four MERGED maps [N,n,H,W] back to back (N*H*W*(6+2J) floats): wh and hps at a centre peak (y, x) are
+ * (image(y, x) + sign * twin'(y, W-1-x)) / 2 with cp_flip_merge_pairs_f32's channel swap and sign (modes 0 and 2), each side bit for
+ * bit what cp_head_points_f32 writes for that pixel of that image; reg and hp_offset are the image's own values (mode 3).  Same
+ * write footprint and the same limits as cp_head_points_f32; one launch. */
+int cp_head_points_pairs_f32(const float* feat, int featLd, const int* ws_inds, const int* perm, const float* w1, const float* b1,
+                             const float* w2, const float* b2, float* out, int N, int H, int W, int C, int J, int K, int hc,
+                             void* stream);
 
 /* ---- plan handle: a whole network behind three calls -----------------------------
  * Replaces BackBoneWithHead.forward (lib/models/model.py:57-59: head_model(backbone_model(x))) for one compiled
@@ -280,8 +290,9 @@ int cp_plan_output(const cp_plan* plan, int i, float** dev_ptr, int shape[4]);
 int cp_plan_forward(cp_plan* plan, const float* images, void* stream);
 int cp_plan_process(cp_plan* plan, const float* images, int K, float* dets, void* stream);
 int cp_plan_destroy(cp_plan* plan);
-/* 1 when the plan was compiled detections-only (Engine(..., decode_k=K, dets_only=True): it holds a cp_head_points_f32 launch),
- * else 0 (-1: NULL plan).  Such a plan still has six outputs, but outputs 1, 2, 3 and 5 (wh, hps, reg, hp_offset) are valid only at
+/* 1 when the plan was compiled detections-only (Engine(..., decode_k=K, dets_only=True): it holds a cp_head_points_f32 launch; or
+ * Engine(..., decode_k=K, flip_dets_only=True): a cp_head_points_pairs_f32 launch, and cp_plan_flip_test says 1 as well, the four
+ * sparse outputs then being the [N] MERGED maps), else 0 (-1: NULL plan).  Such a plan still has six outputs, but outputs 1, 2, 3 and 5 (wh, hps, reg, hp_offset) are valid only at
  * the peaks the plan's own decode found; cp_plan_process / cp_pipeline_process need K = the plan's decode_k. */
 int cp_plan_dets_only(const cp_plan* plan);
 /* 1 when the plan was compiled for the flip test (Engine(..., decode_k=K, flip_test=True): it holds a cp_flip_merge_pairs_f32
