@@ -6,14 +6,13 @@
 //                                (multi_pose.py:73-75) and soft_nms_39 (lib/external/nms.pyx:172-275) per image, in one launch.
 //
 // The arithmetic is that of prepost.hip (resize_u8_kernel, preprocess_kernel, transform_dets_kernel) and of host_nms.cpp, statement for
-// statement: batched results are bit-identical to the per-image calls.  The one exception is the Gaussian weight of soft-NMS method 2,
-// (float)exp((double)x): the device's double exp is not guaranteed to round like the host C library's, so a decayed score (column 4) may
-// differ in its last float bit per decay.  Compiled with -ffp-contract=off: the coordinate and box arithmetic must round like the host
+// statement (the pre-process statements live in pre_arith.h, shared with frame_sources.hip): batched results are bit-identical to the
+// per-image calls.  The one exception is the Gaussian weight of soft-NMS method 2, (float)exp((double)x): the device's double exp is
+// not guaranteed to round like the host C library's, so a decayed score (column 4) may differ in its last float bit per decay.  Compiled with -ffp-contract=off: the coordinate and box arithmetic must round like the host
 // C++ it restates (host_nms.cpp is built for x86-64, which contracts nothing).
 #include <cmath>
 #include "common.h"
-
-#define BS_THREADS 256
+#include "pre_arith.h"
 
 // ---------------------------------------------------------------------------------------------------- batched pre-process
 // mirror of cp_pre_desc (include/centerpose_hip.h)
@@ -25,24 +24,6 @@ struct PreDesc {
     int slot, pad;          // output batch index of the image (its mirrored twin goes to slot + 1)
 };
 
-__device__ __forceinline__ int bs_sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
-
-// resize_taps of prepost.hip
-__device__ __forceinline__ void bs_resize_taps(int d, double scale, int n, bool vertical, int& i0, int& i1, int& w0, int& w1)
-{
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (!vertical) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= n - 1) { f = 0.f; s = n - 1; }
-    }
-    w1 = bs_sat_short(__float2int_rn(f * 2048.f));
-    w0 = bs_sat_short(__float2int_rn((1.f - f) * 2048.f));
-    i0 = min(max(s, 0), n - 1);
-    i1 = min(max(s + 1, 0), n - 1);
-}
-
 // blockIdx.y: image; blockIdx.x: grid-stride tiles of its resized pixels.  Images without a resize leave at once.
 __global__ __launch_bounds__(BS_THREADS) void resize_batch_u8_kernel(const unsigned char* __restrict__ staging, unsigned char* __restrict__ scratch,
                                                                      const PreDesc* __restrict__ table)
@@ -51,58 +32,15 @@ __global__ __launch_bounds__(BS_THREADS) void resize_batch_u8_kernel(const unsig
     if (d.mid_off < 0) return;
     const int H = d.H, W = d.W, NH = d.NH, NW = d.NW, total = NH * NW;
     const double scale_x = (double)W / NW, scale_y = (double)H / NH;
-    const unsigned char* src = staging + d.src_off;
+    const BsPacked src = {staging + d.src_off, W};
     unsigned char* dst = scratch + d.mid_off;
     for (int i = blockIdx.x * BS_THREADS + threadIdx.x; i < total; i += gridDim.x * BS_THREADS) {
         const int dy = i / NW, dx = i - dy * NW;
-        int x0, x1, a0, a1, y0, y1, b0, b1;
-        bs_resize_taps(dx, scale_x, W, false, x0, x1, a0, a1);
-        bs_resize_taps(dy, scale_y, H, true, y0, y1, b0, b1);
-        const unsigned char* r0 = src + (size_t)y0 * W * 3;
-        const unsigned char* r1 = src + (size_t)y1 * W * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int S0 = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;
-            const int S1 = r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1;
-            const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-            dst[(size_t)i * 3 + c] = (unsigned char)min(max(v, 0), 255);
-        }
+        bs_resize_pixel(src, H, W, scale_x, scale_y, dx, dy, dst + (size_t)i * 3);
     }
 }
 
-struct BsNorm { float mean[3], sd[3]; };
-
-// one destination pixel of preprocess_kernel (prepost.hip): the three normalised channels
-__device__ __forceinline__ void bs_warp_pixel(const unsigned char* __restrict__ img, int H, int W, const double* m, int ox, int oy,
-                                              const BsNorm& nm, float r[3])
-{
-    const int adelta = (int)__double2ll_rn(m[0] * (double)ox * 1024.0);
-    const int bdelta = (int)__double2ll_rn(m[3] * (double)ox * 1024.0);
-    const int X0 = (int)__double2ll_rn((m[1] * (double)oy + m[2]) * 1024.0) + 16;
-    const int Y0 = (int)__double2ll_rn((m[4] * (double)oy + m[5]) * 1024.0) + 16;
-    const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    const int sx = bs_sat_short(X >> 5), sy = bs_sat_short(Y >> 5);
-    const int fx = X & 31, fy = Y & 31;
-    int w[4] = {(32 - fy) * (32 - fx) * 32, (32 - fy) * fx * 32, fy * (32 - fx) * 32, fy * fx * 32};
-    if (w[0] > 32767) w[0] = 32767;
-    int acc[3] = {0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int yy = sy + (t >> 1), xx = sx + (t & 1);
-        if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;      // constant border, value 0
-        const unsigned char* p = img + ((size_t)yy * W + xx) * 3;
-        acc[0] += w[t] * p[0]; acc[1] += w[t] * p[1]; acc[2] += w[t] * p[2];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int u8 = min(max((acc[c] + (1 << 14)) >> 15, 0), 255);
-        r[c] = (float)((((double)u8 / 255.0) - (double)nm.mean[c]) / (double)nm.sd[c]);
-    }
-}
-
-// blockIdx.y: image; blockIdx.x: grid-stride tiles of its OH x OW destination pixels.  VEC (OW % 4 == 0, 16-B aligned output): a lane
-// owns four consecutive ox and stores one float4 per channel plane, and the reversed float4 into the twin's plane
-// (flip_merge_pairs_kernel<vec4>'s shape: OW - 4 - ox0 is a multiple of 4 as well).
+// blockIdx.y: image; blockIdx.x: grid-stride tiles of its OH x OW destination pixels (bs_warp_image, pre_arith.h).
 template <bool VEC>
 __global__ __launch_bounds__(BS_THREADS) void preprocess_batch_kernel(const unsigned char* __restrict__ staging,
                                                                       const unsigned char* __restrict__ scratch,
@@ -110,38 +48,13 @@ __global__ __launch_bounds__(BS_THREADS) void preprocess_batch_kernel(const unsi
                                                                       BsNorm nm, int flip)
 {
     const PreDesc& d = table[blockIdx.y];
-    const unsigned char* img = d.mid_off < 0 ? staging + d.src_off : scratch + d.mid_off;
-    const int H = d.NH, W = d.NW;
+    const BsPacked src = {d.mid_off < 0 ? staging + d.src_off : scratch + d.mid_off, d.NW};
     double m[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) m[k] = d.mi[k];
     const size_t total = (size_t)OH * OW;
     float* o = out + (size_t)d.slot * 3 * total;
-    float* tw = o + 3 * total;
-    const int Wq = VEC ? OW >> 2 : OW, items = OH * Wq;
-    for (int i = blockIdx.x * BS_THREADS + threadIdx.x; i < items; i += gridDim.x * BS_THREADS) {
-        const int oy = i / Wq, xq = i - oy * Wq;
-        if (VEC) {
-            const int ox0 = 4 * xq;
-            float r[4][3];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bs_warp_pixel(img, H, W, m, ox0 + k, oy, nm, r[k]);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                *reinterpret_cast<float4*>(o + c * total + (size_t)oy * OW + ox0) = make_float4(r[0][c], r[1][c], r[2][c], r[3][c]);
-                if (flip)
-                    *reinterpret_cast<float4*>(tw + c * total + (size_t)oy * OW + (OW - 4 - ox0)) = make_float4(r[3][c], r[2][c], r[1][c], r[0][c]);
-            }
-        } else {
-            float r[3];
-            bs_warp_pixel(img, H, W, m, xq, oy, nm, r);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                o[c * total + (size_t)oy * OW + xq] = r[c];
-                if (flip) tw[c * total + (size_t)oy * OW + (OW - 1 - xq)] = r[c];
-            }
-        }
-    }
+    bs_warp_image<VEC>(src, d.NH, d.NW, m, o, o + 3 * total, OH, OW, nm, flip);
 }
 
 extern "C" int cp_sizeof_pre_desc(void) { return (int)sizeof(PreDesc); }

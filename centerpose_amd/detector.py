@@ -18,6 +18,10 @@ source object, every pixel / tensor stage runs on the device:
 ``run_batch`` (not in the reference, which is one image at a time) takes N images through the same stages batched:
 ``pre_process_batch`` / ``process`` / ``post_process_batch`` / ``merge_outputs_batch`` (csrc/batch_stages.hip), soft-NMS included
 on the device, with one upload and one download per call.
+
+Frames that are ALREADY on the device (CUDA uint8 tensors: [H,W,C] or [C,H,W], C = 3 or 4, BGR or RGB, any strides) go through the
+same entry points -- ``pre_process``, ``pre_process_batch``, ``run_batch``, ``run`` -- and are read in place by csrc/frame_sources.hip:
+no staging copy, no upload, never a ``.contiguous()``; ``run_batch(..., return_device=True)`` hands the rows back without a download.
 """
 import ctypes
 import time
@@ -63,13 +67,14 @@ class StageClock:
 
 
 class _ArraySource:
-    """run() input that still needs pre-processing: an HxWx3 uint8 BGR array (what cv2.imread returns)."""
+    """run() input that still needs pre-processing: an HxWx3 uint8 BGR array (what cv2.imread returns), or one frame on the device
+    (a CUDA uint8 tensor in the given layout / colour order)."""
 
-    def __init__(self, image):
-        self.image = image
+    def __init__(self, image, layout="hwc", color="bgr"):
+        self.image, self.layout, self.color = image, layout, color
 
     def at_scale(self, det, scale, meta):
-        return det.pre_process(self.image, scale, meta)
+        return det.pre_process(self.image, scale, meta, self.layout, self.color)
 
 
 class _PreparedSource:
@@ -98,6 +103,39 @@ def _imread(path):
 # cp_pre_desc (include/centerpose_hip.h): one source image of a batched pre-process
 PRE_DESC = np.dtype([("src_off", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"),
                      ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
+
+
+# cp_frame_desc (include/centerpose_hip.h): one source frame on the device, addressed by pointer and strides
+FRAME_DESC = np.dtype([("base", "<u8"), ("row_stride", "<i8"), ("pix_stride", "<i8"), ("ch_off", "<i8", (3,)), ("mid_off", "<i8"),
+                       ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"), ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
+
+LAYOUTS, COLORS = ("hwc", "chw"), ("bgr", "rgb")
+
+
+def _check_layout(layout, color):
+    if layout not in LAYOUTS:
+        raise _lib.CenterposeHipError("unknown layout %r: one of %s" % (layout, ", ".join(LAYOUTS)))
+    if color not in COLORS:
+        raise _lib.CenterposeHipError("unknown color %r: one of %s" % (color, ", ".join(COLORS)))
+
+
+def frame_geometry(shape, strides, layout="hwc", color="bgr"):
+    """How a uint8 frame of the given shape and strides (in elements == bytes) is addressed: (H, W, row_stride, pix_stride, ch_off),
+    channel k of the network (cv2's B, G, R) of pixel (y, x) at byte y * row_stride + x * pix_stride + ch_off[k] from the frame's first
+    element.  layout "hwc": [H,W,C], "chw": [C,H,W]; C = 3 or 4 (a fourth channel is never read); color: the order of the first three
+    channels in memory.  A pure function of its arguments: nothing is copied, any strides (crops, padded rows, expanded views) go."""
+    _check_layout(layout, color)
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 3 or len(strides) != 3:
+        raise _lib.CenterposeHipError("a frame is 3-D ([H,W,C] or [C,H,W]), got shape %s" % (shape,))
+    (H, W, C), (sh, sw, sc) = (shape, strides) if layout == "hwc" else ((shape[1], shape[2], shape[0]), (strides[1], strides[2], strides[0]))
+    if C not in (3, 4):
+        raise _lib.CenterposeHipError("a frame has 3 or 4 channels (layout %r of shape %s has %d)" % (layout, shape, C))
+    if H <= 0 or W <= 0:
+        raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shape,))
+    if min(sh, sw, sc) < 0:
+        raise _lib.CenterposeHipError("negative strides %s are not addressable" % (strides,))
+    return H, W, sh, sw, ((0, sc, 2 * sc) if color == "bgr" else (2 * sc, sc, 0))
 
 
 class _Staging:
@@ -185,9 +223,20 @@ class BaseDetector(object):
         return (new_h, new_w, inp_h, inp_w, np.array([new_w // 2, new_h // 2], dtype=np.float32),
                 np.array([inp_w, inp_h], dtype=np.float32))
 
-    def pre_process(self, image, scale, meta=None):
+    def pre_process(self, image, scale, meta=None, layout="hwc", color="bgr"):
         """base_detector.py:32-62.  image: HxWx3 uint8 BGR host array -> (images float32 [1 or 2,3,inp_h,inp_w] ON THE
-        DEVICE, meta).  cv2.resize + cv2.warpAffine + normalise + transpose (+ flipped twin) run as HIP kernels."""
+        DEVICE, meta).  cv2.resize + cv2.warpAffine + normalise + transpose (+ flipped twin) run as HIP kernels.
+        image may also be one frame that is already on the device: a CUDA uint8 tensor [H,W,C] (layout="hwc") or [C,H,W] ("chw"),
+        C = 3 or 4, channels in memory in `color` order ("bgr" / "rgb"), any strides.  It is read in place (no copy, no upload) by
+        pre_process_batch's device path, whose stream-order and lifetime rules apply; the result is bit-identical to the same call
+        on the equivalent HxWx3 BGR host array.  Host arrays are cv2's layout: another layout / color raises for them."""
+        if isinstance(image, torch.Tensor):
+            if image.dim() != 3:
+                raise _lib.CenterposeHipError("pre_process takes one 3-D frame tensor, got shape %s (N frames: pre_process_batch)"
+                                              % (tuple(image.shape),))
+            x, metas = self.pre_process_batch([image], scale, layout, color)
+            return x, metas[0]
+        self._host_layout_only(layout, color)
         if not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3):
             raise _lib.CenterposeHipError("pre_process expects an HxWx3 uint8 array (cv2.imread layout); there is no host fallback")
         height, width = image.shape[0:2]
@@ -237,6 +286,51 @@ class BaseDetector(object):
         return images
 
     @staticmethod
+    def _host_layout_only(layout, color):
+        _check_layout(layout, color)      # unknown names raise
+        if (layout, color) != ("hwc", "bgr"):
+            raise _lib.CenterposeHipError("host arrays are taken in cv2's layout (HxWx3, BGR): layout=%r / color=%r apply to frames "
+                                          "on the device (CUDA uint8 tensors) only" % (layout, color))
+
+    def _model_device(self):
+        """The card the model's plans live on, with its index ("cuda" alone means the current device, as everywhere here)."""
+        device = torch.device(self.model.device)
+        return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _frame(self, t, layout, color):
+        """One device frame -> (address of pixel (0,0), H, W, row_stride, pix_stride, ch_off), all from the tensor's own shape,
+        strides and data pointer: a valid view cannot address outside its storage.  The tensor is never copied or made contiguous."""
+        if not t.is_cuda:
+            raise _lib.CenterposeHipError("a frame tensor on %s: frames given as tensors must be on the model's GPU (host frames are "
+                                          "passed as numpy arrays); there is no host fallback" % t.device)
+        if t.dtype != torch.uint8:
+            raise _lib.CenterposeHipError("a frame tensor must be uint8 (got %s)" % t.dtype)
+        geometry = frame_geometry(t.shape, t.stride(), layout, color)
+        device = self._model_device()
+        if t.device != device:
+            raise _lib.CenterposeHipError("a frame tensor on %s, the model is on %s" % (t.device, device))
+        return (t.data_ptr(),) + geometry
+
+    def _batch_input(self, images, layout, color):
+        """What a batched call was given -> (images as a list, frames): frames is None for host arrays (the staging path), else one
+        `_frame` per device tensor.  One 4-D tensor means N frames ([N,H,W,C] or [N,C,H,W])."""
+        _check_layout(layout, color)      # unknown names raise, whatever the input
+        if isinstance(images, torch.Tensor):
+            if images.dim() != 4:
+                raise _lib.CenterposeHipError("one tensor for N frames is 4-D ([N,H,W,C] or [N,C,H,W]), got shape %s; pass a list of "
+                                              "3-D frames otherwise" % (tuple(images.shape),))
+            images = images.unbind(0)
+        images = list(images)
+        tensors = sum(isinstance(im, torch.Tensor) for im in images)
+        if tensors == 0:
+            if images:
+                self._host_layout_only(layout, color)
+            return self._check_batch(images), None
+        if tensors != len(images):
+            raise _lib.CenterposeHipError("host arrays and device tensors mixed in one call: pass all frames one way")
+        return images, [self._frame(t, layout, color) for t in images]
+
+    @staticmethod
     def _batch_layout(shapes):
         """Byte offset of every image in the one staging buffer (images back to back) and the buffer's size."""
         offsets, pos = [], 0
@@ -254,12 +348,13 @@ class BaseDetector(object):
             groups.setdefault(key, []).append(i)
         return list(groups.values())
 
-    def _pre_table(self, shapes, offsets, idx, scale):
-        """The descriptor table (PRE_DESC) of one batched pre-process: images `idx` at `scale`, which must share one network input shape
-        -> (table, scratch_bytes, inp_h, inp_w, metas).  Geometry, matrix and meta per image are pre_process's."""
+    def _pre_table(self, shapes, offsets, idx, scale, frames=None):
+        """The descriptor table of one batched pre-process: images `idx` at `scale`, which must share one network input shape
+        -> (table, scratch_bytes, inp_h, inp_w, metas).  Geometry, matrix and meta per image are pre_process's.  PRE_DESC rows with the
+        images' staging `offsets`, or, with `frames` (`_frame` per image), FRAME_DESC rows that address the frames where they lie."""
         nb = 2 if self.cfg.TEST.FLIP_TEST else 1
         down = self.cfg.MODEL.DOWN_RATIO
-        table = np.zeros(len(idx), PRE_DESC)
+        table = np.zeros(len(idx), PRE_DESC if frames is None else FRAME_DESC)
         metas, scratch, inp = [], 0, None
         for j, i in enumerate(idx):
             height, width = shapes[i]
@@ -272,7 +367,11 @@ class BaseDetector(object):
                 raise _lib.CenterposeHipError("pre_process_batch needs one network input shape per call (%s and %s at scale %s): "
                                               "run_batch groups mixed sizes" % (inp, (inp_h, inp_w), scale))
             d = table[j]
-            d["src_off"], d["H"], d["W"], d["NH"], d["NW"], d["slot"] = offsets[i], height, width, new_h, new_w, nb * j
+            d["H"], d["W"], d["NH"], d["NW"], d["slot"] = height, width, new_h, new_w, nb * j
+            if frames is None:
+                d["src_off"] = offsets[i]
+            else:
+                d["base"], _, _, d["row_stride"], d["pix_stride"], d["ch_off"] = frames[i]
             if (new_h, new_w) != (height, width):
                 d["mid_off"] = scratch
                 scratch += new_h * new_w * 3
@@ -312,13 +411,7 @@ class BaseDetector(object):
 
     def _launch_pre(self, staging, table_dev, table, scratch_bytes, inp_h, inp_w):
         """cp_preprocess_batch_u8_f32 for one table -> float32 [nb * N, 3, inp_h, inp_w] on the device."""
-        nb = 2 if self.cfg.TEST.FLIP_TEST else 1
-        n = len(table)
-        x = torch.empty((nb * n, 3, inp_h, inp_w), dtype=torch.float32, device="cuda")
-        scratch = torch.empty((max(scratch_bytes, 1),), dtype=torch.uint8, device="cuda")
-        mean = np.ascontiguousarray(self.mean.reshape(3), np.float32)
-        std = np.ascontiguousarray(self.std.reshape(3), np.float32)
-        table = np.ascontiguousarray(table)
+        nb, n, x, scratch, mean, std, table = self._pre_buffers(table, scratch_bytes, inp_h, inp_w)
         rc = _lib.lib().cp_preprocess_batch_u8_f32(
             ctypes.c_void_p(staging.data_ptr()), ctypes.c_size_t(staging.numel()), ctypes.c_void_p(scratch.data_ptr()),
             ctypes.c_size_t(scratch_bytes), ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, _lib.ptr(x),
@@ -327,14 +420,46 @@ class BaseDetector(object):
         _lib.check(rc, "cp_preprocess_batch_u8_f32")
         return x
 
-    def pre_process_batch(self, images, scale):
+    def _pre_buffers(self, table, scratch_bytes, inp_h, inp_w):
+        """What both pre-process launches need: (nb, N, the output batch, the scratch buffer, mean, std, the table contiguous)."""
+        nb = 2 if self.cfg.TEST.FLIP_TEST else 1
+        n = len(table)
+        x = torch.empty((nb * n, 3, inp_h, inp_w), dtype=torch.float32, device="cuda")
+        scratch = torch.empty((max(scratch_bytes, 1),), dtype=torch.uint8, device="cuda")
+        mean = np.ascontiguousarray(self.mean.reshape(3), np.float32)
+        std = np.ascontiguousarray(self.std.reshape(3), np.float32)
+        return nb, n, x, scratch, mean, std, np.ascontiguousarray(table)
+
+    def _launch_frames(self, table_dev, table, scratch_bytes, inp_h, inp_w):
+        """cp_preprocess_frames_u8_f32 for one FRAME_DESC table -> float32 [nb * N, 3, inp_h, inp_w] on the device."""
+        nb, n, x, scratch, mean, std, table = self._pre_buffers(table, scratch_bytes, inp_h, inp_w)
+        rc = _lib.lib().cp_preprocess_frames_u8_f32(
+            ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, ctypes.c_void_p(scratch.data_ptr()),
+            ctypes.c_size_t(scratch_bytes), _lib.ptr(x), nb * n, inp_h, inp_w, mean.ctypes.data_as(ctypes.c_void_p),
+            std.ctypes.data_as(ctypes.c_void_p), 1 if nb == 2 else 0, _lib.stream())
+        _lib.check(rc, "cp_preprocess_frames_u8_f32")
+        return x
+
+    def pre_process_batch(self, images, scale, layout="hwc", color="bgr"):
         """pre_process for N images that share one network input shape at `scale` (any sizes with FIX_RES) -> (float32
         [nb * N, 3, inp_h, inp_w] ON THE DEVICE, list of N meta dicts); nb = 2 with FLIP_TEST: image n at 2n, its mirrored twin at
         2n + 1, the layout `process` takes.  One upload of the images, one of the descriptor table, one resize launch (if any image
-        is resized) and one warp launch; every image bit-identical to pre_process(image, scale)."""
-        images = self._check_batch(images)
+        is resized) and one warp launch; every image bit-identical to pre_process(image, scale).
+        Frames on the device: `images` is a list of CUDA uint8 tensors, each [H,W,C] (layout="hwc") or [C,H,W] ("chw") with C = 3 or 4,
+        channels in `color` order ("bgr" / "rgb") and any strides (crops, padded rows, planar, expanded), or one 4-D tensor of N such
+        frames.  They are read where they lie (cp_preprocess_frames_u8_f32): the descriptor table is the only upload, there is no
+        staging copy and no `.contiguous()`; bit-identical to the call on the equivalent HxWx3 BGR host arrays.  The launches go to
+        the current stream: whatever produced the frames must be ordered before this call on that stream, and a frame must stay
+        allocated until the launches have run -- a tensor that was allocated on another stream needs `record_stream` for the
+        current one before it is released.  Host arrays and tensors cannot be mixed; host arrays take layout / color defaults only."""
+        images, frames = self._batch_input(images, layout, color)
         if not images:
             raise _lib.CenterposeHipError("pre_process_batch needs at least one image")
+        if frames is not None:
+            shapes = [f[1:3] for f in frames]
+            table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, None, list(range(len(frames))), scale, frames)
+            table_dev, = self._upload_table([table])
+            return self._launch_frames(table_dev, table, scratch_bytes, inp_h, inp_w), metas
         shapes = [im.shape[0:2] for im in images]
         offsets, nbytes = self._batch_layout(shapes)
         table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale)
@@ -354,7 +479,7 @@ class BaseDetector(object):
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images, dets_only=False):
+    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -362,20 +487,28 @@ class BaseDetector(object):
         synchronisation, so there are no stage timers: run() is the timed form.  With FLIP_TEST and a head gated off by cfg.LOSS
         `process` takes one pair at a time; the stages around it stay batched.
         dets_only=True: every group goes through `process_dets` (a detections-only plan, under FLIP_TEST too) instead of `process`;
-        ValueError where `process_dets` raises it."""
-        images = self._check_batch(images)
+        ValueError where `process_dets` raises it.
+        Frames on the device: `images` as for pre_process_batch (a list of CUDA uint8 tensors or one 4-D tensor, `layout`, `color`);
+        they are read in place, the descriptor tables are the call's only upload, and the results equal those of the same frames
+        given as host arrays.  The same stream-order and lifetime rules hold.
+        return_device=True (host or device input): the rows as ONE device tensor float32 [N, S*K, 56] in input order instead of the
+        list -- no download and no synchronisation; the tensor is ready in the current stream's order."""
+        images, frames = self._batch_input(images, layout, color)
         if not images:
-            return []
-        shapes = [im.shape[0:2] for im in images]
-        offsets, nbytes = self._batch_layout(shapes)
+            return torch.empty((0, 0, 56), dtype=torch.float32, device="cuda") if return_device else []
+        shapes = [im.shape[0:2] for im in images] if frames is None else [f[1:3] for f in frames]
+        offsets, nbytes = self._batch_layout(shapes) if frames is None else (None, 0)
         groups = self._batch_groups(shapes)
         work, parts = [], []
         for idx in groups:
             for scale in self.scales:
-                table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, idx, scale)
+                table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, idx, scale, frames)
                 work.append((table, scratch_bytes, inp_h, inp_w))
                 parts += [table, self._inverse_affines(metas)]
-        staging = self._upload_images(images, offsets, nbytes)
+        order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
+        if return_device and len(groups) > 1:
+            parts.append(np.argsort(np.asarray(order, np.int64)).astype(np.int64))       # rides in the one table upload
+        staging = self._upload_images(images, offsets, nbytes) if frames is None else None
         parts = self._upload_table(parts)
         merged = []
         for g, idx in enumerate(groups):
@@ -383,28 +516,36 @@ class BaseDetector(object):
             for k, scale in enumerate(self.scales):
                 j = g * len(self.scales) + k
                 table, scratch_bytes, inp_h, inp_w = work[j]
-                x = self._launch_pre(staging, parts[2 * j], table, scratch_bytes, inp_h, inp_w)
+                if frames is None:
+                    x = self._launch_pre(staging, parts[2 * j], table, scratch_bytes, inp_h, inp_w)
+                else:
+                    x = self._launch_frames(parts[2 * j], table, scratch_bytes, inp_h, inp_w)
                 dets = self.process_dets(x) if dets_only else self._process_batch(x)
                 per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
             merged.append(self.merge_outputs_batch(per_scale))
-        rows = (merged[0] if len(merged) == 1 else torch.cat(merged, 0)).cpu().numpy()          # the one download
+        rows = merged[0] if len(merged) == 1 else torch.cat(merged, 0)
+        if return_device:
+            return rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
+        rows = rows.cpu().numpy()                                                               # the one download
         results = [None] * len(images)
-        for r, i in enumerate(i for idx in groups for i in idx):
+        for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
         return results
 
-    def _source(self, x):
-        if isinstance(x, np.ndarray):
-            return _ArraySource(x)
+    def _source(self, x, layout="hwc", color="bgr"):
+        if isinstance(x, (np.ndarray, torch.Tensor)):
+            return _ArraySource(x, layout, color)
         if isinstance(x, str):
-            return _ArraySource(_imread(x))
+            return _ArraySource(_imread(x), layout, color)
         return _PreparedSource(x)
 
-    def run(self, image_or_path_or_tensor, meta=None):
+    def run(self, image_or_path_or_tensor, meta=None, layout="hwc", color="bgr"):
         """base_detector.py:79-140: every TEST_SCALES entry through pre_process -> process -> post_process, then
-        merge_outputs; returns {'results': {1: rows}, 'tot', 'load', 'pre', 'net', 'dec', 'post', 'merge'}."""
+        merge_outputs; returns {'results': {1: rows}, 'tot', 'load', 'pre', 'net', 'dec', 'post', 'merge'}.
+        A CUDA uint8 tensor is one frame on the device in the given `layout` / `color` (see pre_process): read in place, same results
+        as the equivalent host array."""
         clock = StageClock(torch.cuda.synchronize)
-        source = self._source(image_or_path_or_tensor)
+        source = self._source(image_or_path_or_tensor, layout, color)
         clock.lap("load", sync=False)
         per_scale = []
         for scale in self.scales:

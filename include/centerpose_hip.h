@@ -7,6 +7,8 @@
  * (thread-local).  The kernel entry points never synchronise the host and never allocate device memory; kernels
  * are enqueued on `stream` only (so a caller may capture a sequence of calls into a hipGraph).  The plan handle
  * (cp_plan_*) is the one exception and says so.
+ * Source images reach the pre-process either through one staging buffer (cp_pre_desc) or, when they are on the device already, in
+ * place through a per-frame address and strides (cp_frame_desc); both are read when `stream` reaches the launches.
  *
  * File:line citations are relative to the reference checkout (/root/reference).
  * Activation layout: NHWC float32, `ld` = floats between consecutive pixels (>= C).
@@ -354,6 +356,33 @@ int cp_preprocess_batch_u8_f32(const unsigned char* staging, size_t staging_byte
 int cp_post_merge_max_rows(void);
 int cp_post_merge_batch_f32(int S, const float* const* dets, const double* trans, const float* scales, int N, int K, float* out,
                             int* n_keep, int nms, float sigma, float Nt, float threshold, int method, void* stream);
+
+/* ---- the batched pre-process from frames that are already on the device (run_batch / pre_process of CUDA tensors) -----------------
+ * cp_frame_desc: one source frame, read IN PLACE.  Channel k (k = 0, 1, 2: the order the network and mean / std_ expect, cv2's B, G, R)
+ *   of pixel (y, x) is the byte at base + y * row_stride + x * pix_stride + ch_off[k].  Packed BGR: (3W, 3, {0,1,2}); packed RGB:
+ *   ch_off {2,1,0}; BGRA / RGBA: pix_stride 4 (byte 3 is never read); planar CHW: pix_stride 1, ch_off multiples of the plane stride;
+ *   crops, padded rows and expanded views (a stride of 0) are the same rule.  H, W, NH, NW, mid_off, mi, slot: as in cp_pre_desc; the
+ *   resized intermediate is packed [NH,NW,3] in network channel order.
+ * cp_preprocess_frames_u8_f32: cp_preprocess_batch_u8_f32 with every source addressed through its descriptor instead of an offset into
+ *   one staging buffer: one resize launch (when any frame has mid_off >= 0) and one warp launch, no repack and no copy of a frame,
+ *   bit-identical to cp_preprocess_batch_u8_f32 on the equivalent packed BGR images.  table: DEVICE cp_frame_desc[N], table_host: the
+ *   same descriptors on the HOST, checked before anything is launched: base non-null, sizes positive and below 2^29 pixels, strides and
+ *   ch_off >= 0, the largest addressed offset below 2^62, mid_off / scratch / slot as for cp_preprocess_batch_u8_f32, N <= 65535.  The
+ *   size of a frame's allocation is NOT known to the library: the caller vouches that every addressed byte is its own (a tensor view's
+ *   shape, strides and data pointer do).  The frames are read when `stream` reaches the launches: they must have been produced in
+ *   stream order before this call and stay allocated until that work has run.  cp_last_kernel(): preprocess_frames_kernel<vec4|scalar>. */
+typedef struct cp_frame_desc {      /* 128 bytes */
+    const unsigned char* base;      /* DEVICE address of pixel (0,0) */
+    long long row_stride, pix_stride;   /* bytes */
+    long long ch_off[3];            /* bytes from a pixel's address to network channel 0, 1, 2 */
+    long long mid_off;              /* as cp_pre_desc: offset of the resized image in scratch, < 0: no resize */
+    int H, W, NH, NW;
+    double mi[6];                   /* inverted warp matrix (cp_invert_warp) */
+    int slot, pad;
+} cp_frame_desc;
+int cp_sizeof_frame_desc(void);
+int cp_preprocess_frames_u8_f32(const void* table, const void* table_host, int N, unsigned char* scratch, size_t scratch_bytes,
+                                float* out, int out_batch, int OH, int OW, const float* mean, const float* std_, int flip, void* stream);
 
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
