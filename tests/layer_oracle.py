@@ -11,7 +11,8 @@
 * walks the same networks on the CPU alone (``CpuWalker``) to measure how far a float32 evaluation -- direct, F(2x2,3x3) and
   F(2x4,3x3) Winograd -- is from the float64 one in the same units: ``LAYER_TOL`` is four times that.
 
-Nothing here reads the device kernels' sources or results to set a bound.
+Nothing here reads the device kernels' sources or results to set a bound.  tests/launch_oracle.py judges single forced launches -- the
+kernel variants these plans never dispatch to -- with the same pieces.
 """
 import collections
 
@@ -67,11 +68,17 @@ def spread_bn(sd):
     out = dict(sd)
     for k, v in sd.items():
         if k.endswith(".weight") and v.dim() == 1 and k[:-7] + ".running_var" in sd:
-            f = torch.ones_like(v)
-            f[0::5] *= 1e-2
-            f[0::7] *= 1e+1
-            out[k] = v * (f / f.pow(2).mean().sqrt())
+            out[k] = v * spread_factors(v.numel()).to(v)
     return out
+
+
+def spread_factors(n):
+    """the per-channel factors of `spread_bn` for n channels (float32), already divided by their RMS: for a launch that has no BN
+    (the head branches) the same spread goes on the rows of the weights"""
+    f = torch.ones(n)
+    f[0::5] *= 1e-2
+    f[0::7] *= 1e+1
+    return f / f.pow(2).mean().sqrt()
 
 
 def checkpoint(arch, seed, H, W):
@@ -277,6 +284,15 @@ def dcn_stage(sd, x, om, conv, bn, co, dt):
     return Out(F.relu(v), A, 9 * C + 4)
 
 
+def head_branch(sd, xv, c3, c1, hc, n, act, dt, wino=None):
+    """one KeypointHead branch: conv3x3 `c3` + bias + ReLU -> conv1x1 `c1` + bias (+ `act`) of xv (already in `dt`) -> Out; K counts both
+    sums, A carries the mid activations' own magnitude sums through the 1x1"""
+    mid = _affine(xv, xv.abs(), sd[c3 + ".weight"], *_fold(sd, None, c3 + ".bias", hc, dt), act=True, pad=1, wino=wino)
+    o = _affine(mid.val, mid.A if mid.A is not None else mid.val.abs(), sd[c1 + ".weight"], *_fold(sd, None, c1 + ".bias", n, dt), act=act)
+    o.K += mid.K
+    return o
+
+
 def evaluate(hook, sd, args, get, dt, wino=None, om=None):
     """The hook `hook(*args)` in plain torch, dtype `dt`.  `get(view, nchw=False)` -> the input's LOGICAL channels as a float32 NCHW
     CPU tensor.  -> [Out] in the order of the hook's outputs.  wino: None (direct) / "wino" / "wino24": how 3x3 / s1 / p1 convs are
@@ -351,15 +367,8 @@ def evaluate(hook, sd, args, get, dt, wino=None, om=None):
     if hook == "emit_head":
         feat, p, hc = args
         xv = g(feat)
-        outs = []
-        for h, n in nets.HEADS:
-            mid = _affine(xv, xv.abs(), sd["%s.%s.0.weight" % (p, h)], *_fold(sd, None, "%s.%s.0.bias" % (p, h), hc, dt), act=True, pad=1,
-                          wino=wino)
-            o = _affine(mid.val, mid.A if mid.A is not None else mid.val.abs(), sd["%s.%s.2.weight" % (p, h)],
-                        *_fold(sd, None, "%s.%s.2.bias" % (p, h), n, dt), act="sigmoid" if h in SIGMOID_HEADS else None)
-            o.K += mid.K
-            outs.append(o)
-        return outs
+        return [head_branch(sd, xv, "%s.%s.0" % (p, h), "%s.%s.2" % (p, h), hc, n, "sigmoid" if h in SIGMOID_HEADS else None, dt, wino)
+                for h, n in nets.HEADS]
     raise ValueError(hook)
 
 
@@ -456,12 +465,17 @@ def dcn_liveness(om):
     return (float(((h > -1) & (w > -1) & (h < H) & (w < W)).double().mean()), float(((m > 0.01) & (m < 0.99)).double().mean()))
 
 
+def sigmoid_liveness(v):
+    """fraction of a sigmoid map in (1e-6, 1 - 1e-6)"""
+    return float(((v > 1e-6) & (v < 1 - 1e-6)).double().mean())
+
+
 def liveness(hook, vals, om=None):
     """{key of LIVE_FLOOR: fraction} of one record: `om` the logits an emit_dcn samples with, `vals` the outputs of an emit_head"""
     if hook == "emit_dcn":
         return dict(zip(("dcn_samples", "dcn_masks"), dcn_liveness(om)))
     if hook == "emit_head":
-        return {"sigmoid": min(float(((v > 1e-6) & (v < 1 - 1e-6)).double().mean()) for (h, _), v in zip(nets.HEADS, vals) if h in SIGMOID_HEADS)}
+        return {"sigmoid": min(sigmoid_liveness(v) for (h, _), v in zip(nets.HEADS, vals) if h in SIGMOID_HEADS)}
     return {}
 
 

@@ -1,6 +1,8 @@
 """GPU: fused conv / DCNv2 / pooling / upsampling kernels (through the C ABI) against plain
 torch-CPU fp32 references of the same op and the scalar C DCN oracle.
-Tolerance: fp32 in / fp32 accumulate on MFMA -> |err| <= 2e-4 * max|ref| (summation order only)."""
+Tolerance: fp32 in / fp32 accumulate on MFMA -> |err| <= 2e-4 * max|ref| (summation order only).
+The per-element judgement of the variants forced here through `tile=` / `ksplit=` / `wino24=` (|out - ref64| <= c u A on post-ReLU data
+with a per-channel scale spread) lives in tests/test_variant_parity_hip.py."""
 import numpy as np
 import pytest
 import torch

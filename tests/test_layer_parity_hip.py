@@ -9,7 +9,10 @@ file).  Run with -s for the per-arch report: launches checked, kernels covered, 
 The single-launch conv3x3_wino24_kernel wants >= 256 blocks of 16 x 16 pixels x 32 channels (`ops.wino24_wanted`), which no layer has
 at these sizes: two cases lift that floor with CP_WINO24_RULE=32,16,1, as tests/test_engine_hip.py does, so that the plans' 3x3 layers
 run on it.  Not in MUST_COVER because it cannot be reached at these sizes: the fused head kernels (head3x3_1x1: `ops.head3x3_1x1_eligible`
-wants >= 512 blocks of 8 x 16 pixels, the 40 x 24 head map of B = 3 has 30, and no switch lowers that floor).
+wants >= 512 blocks of 8 x 16 pixels, the 40 x 24 head map of B = 3 has 30, and no switch lowers that floor).  They, and every other
+instantiation the launchers pick only for large block counts (128-row GEMM tiles, the 64 x 128 DCN tile, the 64-channel and V-stationary
+Winograd blocks, the tile walk of the persistent kernels), are judged by the same oracle one forced launch at a time in
+tests/test_variant_parity_hip.py.
 """
 import pytest
 
