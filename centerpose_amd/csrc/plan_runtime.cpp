@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "schedule_waits.h"
 
 extern "C" {
 struct cp_conv_desc;
@@ -223,40 +224,38 @@ struct SchedOp { const Op* op; int stream; int buf_base; };
 int run_schedule(const std::vector<SchedOp>& ops, size_t nb, hipStream_t main, hipStream_t side, std::vector<hipEvent_t>& ev)
 {
     const size_t n = ops.size();
-    std::vector<int> last_writer(nb, -1);
-    std::vector<std::vector<int>> readers(nb);
-    hipStream_t st[2] = {main, side};
-    int waited[2] = {-1, -1}, tail[2] = {-1, -1};
-    ev.assign(n + 1, nullptr);
-    if (hipEventCreateWithFlags(&ev[n], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[n], main) != hipSuccess ||
-        hipStreamWaitEvent(side, ev[n], 0) != hipSuccess) { cp_set_error("plan: fork of the side stream failed"); return 2; }
+    // the waits come from the host-only bookkeeping of schedule_waits.h (also exported as cp_schedule_waits): one code path
+    std::vector<int> streams(n), nptr(n), out_index(n), bufids, wait_for;
+    bool any_side = false;
     for (size_t i = 0; i < n; ++i) {
         const Op& o = *ops[i].op;
-        const int me = ops[i].stream ? 1 : 0, other = me ^ 1, base = ops[i].buf_base;
-        int need = -1;                                   // youngest op of the other stream this one must follow
-        auto follow = [&](int j) { if (j >= 0 && (ops[j].stream ? 1 : 0) == other && j > need) need = j; };
-        for (size_t k = 0; k < o.ptrs.size(); ++k) {
-            if (o.bufid[k] < 0) continue;
-            const int b = base + o.bufid[k];
-            follow(last_writer[b]);
-            if (k == o.out_index) for (int j : readers[b]) follow(j);
-        }
-        if (need > waited[me]) {
-            if (hipStreamWaitEvent(st[me], ev[need], 0) != hipSuccess) { cp_set_error("plan: event wait failed"); return 2; }
-            waited[me] = need;
-        }
+        streams[i] = ops[i].stream ? 1 : 0;
+        any_side = any_side || streams[i] != 0;
+        nptr[i] = (int)o.ptrs.size();
+        out_index[i] = (int)o.out_index;
+        for (int b : o.bufid) bufids.push_back(b < 0 ? -1 : ops[i].buf_base + b);
+    }
+    if (!schedule_waits((int)n, streams.data(), nptr.data(), bufids.data(), out_index.data(), (int)nb, wait_for)) {
+        cp_set_error("plan: buffer id out of range in the schedule");
+        return 2;
+    }
+    hipStream_t st[2] = {main, side};
+    int tail[2] = {-1, -1};
+    ev.assign(n + 1, nullptr);
+    // the side stream joins the capture only when an op runs there: a fork without a join would leave the capture un-joined
+    // (cp_pipeline_create(depth = 1) on a plan whose ops all sit on stream 0)
+    if (any_side && (hipEventCreateWithFlags(&ev[n], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[n], main) != hipSuccess ||
+                     hipStreamWaitEvent(side, ev[n], 0) != hipSuccess)) { cp_set_error("plan: fork of the side stream failed"); return 2; }
+    for (size_t i = 0; i < n; ++i) {
+        const Op& o = *ops[i].op;
+        const int me = streams[i];
+        if (wait_for[i] >= 0 && hipStreamWaitEvent(st[me], ev[wait_for[i]], 0) != hipSuccess) { cp_set_error("plan: event wait failed"); return 2; }
         if (int rc = run_op(o, st[me])) return rc;
         if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess || hipEventRecord(ev[i], st[me]) != hipSuccess) {
             cp_set_error("plan: event record failed");
             return 2;
         }
         tail[me] = (int)i;
-        for (size_t k = 0; k < o.ptrs.size(); ++k) {
-            if (o.bufid[k] < 0) continue;
-            const int b = base + o.bufid[k];
-            if (k == o.out_index) { last_writer[b] = (int)i; readers[b].clear(); }
-            else readers[b].push_back((int)i);
-        }
     }
     if (tail[1] >= 0 && hipStreamWaitEvent(main, ev[tail[1]], 0) != hipSuccess) { cp_set_error("plan: join of the side stream failed"); return 2; }
     return 0;
@@ -298,6 +297,30 @@ extern "C" uint32_t cp_fnv1a32(const void* data, size_t bytes)
     const unsigned char* p = static_cast<const unsigned char*>(data);
     for (size_t i = 0; i < bytes; ++i) { h ^= p[i]; h *= 16777619u; }
     return h;
+}
+
+// The event waits run_schedule issues for a two-stream schedule, without a plan handle or a device (plan tooling, tests): op i runs on
+// stream streams[i] (0 / 1), names nptr[i] buffers -- bufids, flat: buffer id per pointer, -1 for constants / NULL -- and writes the
+// one at out_index[i]; nbuf = number of buffers.  Writes up to `cap` (op, awaited op) pairs to pairs[2 * cap] and returns how many
+// there are (may exceed cap); -1 for a bad argument.
+extern "C" int cp_schedule_waits(int n_ops, const int* streams, const int* nptr, const int* bufids, const int* out_index, int nbuf,
+                                 int* pairs, int cap)
+{
+    if (n_ops < 0 || nbuf < 0 || cap < 0 || (n_ops > 0 && (!streams || !nptr || !bufids || !out_index)) || (cap > 0 && !pairs)) {
+        cp_set_error("schedule_waits: bad argument");
+        return -1;
+    }
+    for (int i = 0; i < n_ops; ++i)
+        if (nptr[i] < 0 || out_index[i] < 0 || out_index[i] >= (nptr[i] > 0 ? nptr[i] : 1)) { cp_set_error("schedule_waits: op %d: out_index outside its pointers", i); return -1; }
+    std::vector<int> wait_for;
+    if (!schedule_waits(n_ops, streams, nptr, bufids, out_index, nbuf, wait_for)) { cp_set_error("schedule_waits: buffer id out of range"); return -1; }
+    int count = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        if (wait_for[i] < 0) continue;
+        if (count < cap) { pairs[2 * count] = i; pairs[2 * count + 1] = wait_for[i]; }
+        ++count;
+    }
+    return count;
 }
 
 extern "C" int cp_plan_create(const void* blob, size_t bytes, int use_graph, cp_plan** out)

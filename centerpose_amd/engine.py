@@ -529,6 +529,41 @@ def order_is_topological(deps, order):
     return all(pos[j] < pos[i] for i, d in enumerate(deps) for j in d)
 
 
+def capture_waits(deps, nstreams, assign=None):
+    """Placement and event waits of a multi-stream capture, as pure bookkeeping (no device): deps[i] = launches (< i) that launch i
+    must follow, assign[i] = its stream (None: greedy placement).  Returns (where, waits): the stream of every launch and, per launch,
+    the launches whose events its stream waits for before it is enqueued, in issue order.
+    Placement without `assign`: continue the chain of a predecessor that is still the tail of its stream; otherwise take an idle
+    stream.  Waits: streams are FIFO, so per source stream only the youngest predecessor matters, and only if this stream has not
+    already waited for it (or a younger one)."""
+    n = len(deps)
+    has_child = [False] * n
+    for d in deps:
+        for j in d:
+            has_child[j] = True
+    where, tail, waits = [0] * n, [None] * nstreams, [[] for _ in range(n)]
+    waited = [[-1] * nstreams for _ in range(nstreams)]      # waited[s][t]: youngest launch of stream t that s has waited for
+    for i in range(n):
+        sidx = assign[i] if assign is not None else None      # explicit placement (tools/sched_try.py)
+        for j in (sorted(deps[i], reverse=True) if sidx is None else ()):
+            if tail[where[j]] == j:
+                sidx = where[j]
+                break
+        if sidx is None:
+            idle = [k for k in range(nstreams) if tail[k] is None or has_child[tail[k]] is False]
+            sidx = idle[0] if idle else min(range(nstreams), key=lambda k: tail[k])
+        need = {}
+        for j in deps[i]:
+            if where[j] != sidx:
+                need[where[j]] = max(need.get(where[j], -1), j)
+        for t, j in need.items():
+            if j > waited[sidx][t]:
+                waits[i].append(j)
+                waited[sidx][t] = j
+        where[i], tail[sidx] = sidx, i
+    return where, waits
+
+
 class Engine:
     """Static-shape inference engine for one (arch, batch, H, W)."""
 
@@ -764,48 +799,29 @@ class Engine:
         then overlap instead of running back to back."""
         streams = [main] + [torch.cuda.Stream(device=self.device) for _ in range(nstreams - 1)]
         n = len(self.launches)
-        has_child = [False] * n
-        for d in deps:
-            for j in d:
-                has_child[j] = True
-        where, tail, events = [0] * n, [None] * len(streams), [None] * n
+        where, waits = capture_waits(deps, len(streams), assign)      # placement and wait elision: pure bookkeeping
+        tail, events = [None] * len(streams), [None] * n
         fork = torch.cuda.Event()
         fork.record(main)
         joined = [True] + [False] * (len(streams) - 1)
-        waited = [[-1] * len(streams) for _ in streams]      # waited[s][t]: youngest launch of stream t that s has waited for
         for i, (_, _, _, launch) in enumerate(self.launches):
-            # continue the chain of a predecessor that is still the tail of its stream; otherwise take an idle stream
-            sidx = assign[i] if assign is not None else None      # explicit placement (tools/sched_try.py)
-            for j in (sorted(deps[i], reverse=True) if sidx is None else ()):
-                if tail[where[j]] == j:
-                    sidx = where[j]
-                    break
-            if sidx is None:
-                idle = [k for k in range(len(streams)) if tail[k] is None or has_child[tail[k]] is False]
-                sidx = idle[0] if idle else min(range(len(streams)), key=lambda k: tail[k])
+            sidx = where[i]
             st = streams[sidx]
             if not joined[sidx]:
                 st.wait_event(fork)
                 joined[sidx] = True
-            # streams are FIFO: per source stream only the youngest predecessor matters, and only if this stream has
-            # not already waited for it (or a younger one)
-            need = {}
-            for j in deps[i]:
-                if where[j] != sidx:
-                    need[where[j]] = max(need.get(where[j], -1), j)
-            for t, j in need.items():
-                if j > waited[sidx][t]:
-                    st.wait_event(events[j])
-                    waited[sidx][t] = j
+            for j in waits[i]:
+                st.wait_event(events[j])
             with torch.cuda.stream(st):
                 launch.run()
             ev = torch.cuda.Event()
             ev.record(st)
-            events[i], where[i], tail[sidx] = ev, sidx, i
+            events[i], tail[sidx] = ev, i
         for k in range(1, len(streams)):
             if tail[k] is not None:
                 main.wait_event(events[tail[k]])
         self.stream_of_launch = where
+        self.event_waits = waits
         # streams / events must outlive the capture (destroying a capturing stream before hipStreamEndCapture crashes)
         self._capture_refs = (streams, events, fork)
 
@@ -869,6 +885,7 @@ class Engine:
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
                 self.run_eager()
             self.stream_of_launch = [0] * len(self.launches)
+            self.event_waits = [[] for _ in self.launches]
         self.graph = g
 
     def forward(self, images):

@@ -321,6 +321,16 @@ int cp_plan_clone(const cp_plan* plan, cp_plan** out);
 int cp_pipeline_create(cp_plan* const* plans, int depth, cp_pipeline** out);
 int cp_pipeline_process(cp_pipeline* pipe, const float* const* images, int K, float* const* dets, void* stream);
 int cp_pipeline_destroy(cp_pipeline* pipe);
+/* HOST only, no plan handle and no device (plan tooling): the cross-stream event waits the plan runtime issues when it captures a
+ * schedule on its two streams -- the same code path cp_plan_forward / cp_pipeline_process go through.  Op i runs on stream
+ * streams[i] (0 main / 1 side), names nptr[i] pointers whose activation-buffer ids are listed flat, op after op, in bufids (-1:
+ * constant / NULL; the ops of several plan instances: ids offset per instance) and writes the one at out_index[i] (plan.py: `ref`
+ * ids, `out_index`, `stream` of every op); nbuf: number of buffers.  An op follows the last writer of every buffer it names and the
+ * readers of the buffer it writes; of those on the other stream it waits for the youngest, unless its stream already waited for
+ * that op or a younger one.  Writes up to `cap` (op, awaited op) pairs to HOST pairs[2 * cap] and returns how many there are
+ * (possibly more than cap), -1 for a bad argument. */
+int cp_schedule_waits(int n_ops, const int* streams, const int* nptr, const int* bufids, const int* out_index, int nbuf, int* pairs,
+                      int cap);
 /* stream-ordered device-to-device copy (for callers that keep a plan's outputs beyond the next forward) */
 int cp_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import schedule_audit
 from oracle import decode_np, nets_torch
 
 pytestmark = pytest.mark.gpu
@@ -735,6 +736,7 @@ def test_timed_configuration_parity(arch, B):
     outs, dets = eng.process(x.cuda())
     torch.cuda.synchronize()
     assert eng.capture_mode == "2-stream", eng.capture_mode
+    assert schedule_audit.audit(eng.launches, eng.stream_of_launch, eng.event_waits) == []       # no data race in what was captured
     first = [t.clone() for t in outs] + [dets.clone()]
     outs, dets = eng.process(x.cuda())                                                    # (d)
     torch.cuda.synchronize()
@@ -816,6 +818,7 @@ def test_timed_configuration_parity_two_steps_in_flight():
     eng = bench.make_engine("dla_34", B, det=det)
     pipe = det.model.pipeline_for(B, 512, 512, det.cfg.TEST.TOPK, D)
     assert pipe.engines[0] is eng and pipe.capture_mode == "2-stream" and eng.capture_mode == "2-stream"      # (c)
+    assert schedule_audit.audit(pipe.joint.launches, pipe.joint.stream_of_launch, pipe.joint.event_waits) == []
     statics = {e.dets.data_ptr() for e in pipe.engines}
     assert len({k.data_ptr() for k in kept}) == 2 * D and not ({k.data_ptr() for k in kept} & statics)         # (d)
     assert all(torch.equal(k, w[6]) for k, w in zip(kept, want + want))
@@ -863,6 +866,7 @@ def test_steps_in_flight_same_bits_as_one_after_the_other(arch, depth):
         torch.cuda.synchronize()
         got += [[t.clone() for t in outs] + [dets.clone()] for outs, dets in res]
     assert pipe.capture_mode == "2-stream", pipe.capture_mode
+    assert schedule_audit.audit(pipe.joint.launches, pipe.joint.stream_of_launch, pipe.joint.event_waits) == []
     for i, (g, w) in enumerate(zip(got, want)):
         assert all(torch.equal(a, b) for a, b in zip(g, w)), "step %d differs" % i
     # the joint schedule really interleaves the instances: both capture streams carry launches of more than one instance
