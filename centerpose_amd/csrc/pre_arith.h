@@ -1,28 +1,35 @@
 // The 8-bit fixed-point arithmetic of the batched pre-process, once: cv2.resize (INTER_LINEAR) and cv2.warpAffine + normalise per
 // destination pixel, statement for statement those of prepost.hip (resize_u8_kernel, preprocess_kernel).  batch_stages.hip reads its
 // sources from one packed staging buffer (BsPacked), frame_sources.hip reads every frame in place through a pointer and strides
-// (BsStrided); the statements between the loads are the same functions, so both are bit-identical to the per-image calls.  Include
-// from a translation unit compiled with -ffp-contract=off.
+// (BsStrided), yuv_frames.hip converts (Y, U, V) samples to the three bytes where the taps are loaded (YfSource); the statements
+// between the loads are the same functions, so all are bit-identical to the per-image calls.  Include from a translation unit
+// compiled with -ffp-contract=off.
 #pragma once
 #include "common.h"
 
 #define BS_THREADS 256
 
-// A source image: pixel(y, x) is the address of a pixel, ch(k) the byte offset from it to network channel k (k = 0, 1, 2).
+// A source image: load(y, x, v) puts the three bytes of pixel (y, x), in network channel order (k = 0, 1, 2), into v[0..2].
 // packed uint8 [H,W,3], channels in network order
 struct BsPacked {
     const unsigned char* img;
     int W;
-    __device__ __forceinline__ const unsigned char* pixel(int y, int x) const { return img + ((size_t)y * W + x) * 3; }
-    __device__ __forceinline__ long long ch(int k) const { return k; }
+    __device__ __forceinline__ void load(int y, int x, int v[3]) const
+    {
+        const unsigned char* p = img + ((size_t)y * W + x) * 3;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    }
 };
 
 // any layout: base + y * row + x * pix + off[k] (packed BGR / RGB, BGRA / RGBA, planar CHW, crops, padded rows, expanded views)
 struct BsStrided {
     const unsigned char* base;
     long long row, pix, off[3];
-    __device__ __forceinline__ const unsigned char* pixel(int y, int x) const { return base + (long long)y * row + (long long)x * pix; }
-    __device__ __forceinline__ long long ch(int k) const { return off[k]; }
+    __device__ __forceinline__ void load(int y, int x, int v[3]) const
+    {
+        const unsigned char* p = base + (long long)y * row + (long long)x * pix;
+        v[0] = p[off[0]]; v[1] = p[off[1]]; v[2] = p[off[2]];
+    }
 };
 
 __device__ __forceinline__ int bs_sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
@@ -51,15 +58,15 @@ __device__ __forceinline__ void bs_resize_pixel(const Src& src, int H, int W, do
     int x0, x1, a0, a1, y0, y1, b0, b1;
     bs_resize_taps(dx, scale_x, W, false, x0, x1, a0, a1);
     bs_resize_taps(dy, scale_y, H, true, y0, y1, b0, b1);
-    const unsigned char* p00 = src.pixel(y0, x0);
-    const unsigned char* p01 = src.pixel(y0, x1);
-    const unsigned char* p10 = src.pixel(y1, x0);
-    const unsigned char* p11 = src.pixel(y1, x1);
+    int p00[3], p01[3], p10[3], p11[3];
+    src.load(y0, x0, p00);
+    src.load(y0, x1, p01);
+    src.load(y1, x0, p10);
+    src.load(y1, x1, p11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const long long o = src.ch(c);
-        const int S0 = p00[o] * a0 + p01[o] * a1;
-        const int S1 = p10[o] * a0 + p11[o] * a1;
+        const int S0 = p00[c] * a0 + p01[c] * a1;
+        const int S1 = p10[c] * a0 + p11[c] * a1;
         const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
         dst[c] = (unsigned char)min(max(v, 0), 255);
     }
@@ -85,8 +92,9 @@ __device__ __forceinline__ void bs_warp_pixel(const Src& src, int H, int W, cons
     for (int t = 0; t < 4; ++t) {
         const int yy = sy + (t >> 1), xx = sx + (t & 1);
         if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;      // constant border, value 0
-        const unsigned char* p = src.pixel(yy, xx);
-        acc[0] += w[t] * p[src.ch(0)]; acc[1] += w[t] * p[src.ch(1)]; acc[2] += w[t] * p[src.ch(2)];
+        int p[3];
+        src.load(yy, xx, p);
+        acc[0] += w[t] * p[0]; acc[1] += w[t] * p[1]; acc[2] += w[t] * p[2];
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

@@ -22,6 +22,8 @@ on the device, with one upload and one download per call.
 Frames that are ALREADY on the device (CUDA uint8 tensors: [H,W,C] or [C,H,W], C = 3 or 4, BGR or RGB, any strides) go through the
 same entry points -- ``pre_process``, ``pre_process_batch``, ``run_batch``, ``run`` -- and are read in place by csrc/frame_sources.hip:
 no staging copy, no upload, never a ``.contiguous()``; ``run_batch(..., return_device=True)`` hands the rows back without a download.
+Frames in 4:2:0 YUV (``color="nv12"`` / ``"nv21"`` / ``"i420"``: a decoder's surface or a tuple of plane tensors, any strides) go the
+same way through csrc/yuv_frames.hip, which converts to BGR (``matrix="bt601"`` / ``"bt709"``) where the pixels are loaded.
 """
 import ctypes
 import time
@@ -70,11 +72,11 @@ class _ArraySource:
     """run() input that still needs pre-processing: an HxWx3 uint8 BGR array (what cv2.imread returns), or one frame on the device
     (a CUDA uint8 tensor in the given layout / colour order)."""
 
-    def __init__(self, image, layout="hwc", color="bgr"):
-        self.image, self.layout, self.color = image, layout, color
+    def __init__(self, image, layout="hwc", color="bgr", matrix="bt601"):
+        self.image, self.layout, self.color, self.matrix = image, layout, color, matrix
 
     def at_scale(self, det, scale, meta):
-        return det.pre_process(self.image, scale, meta, self.layout, self.color)
+        return det.pre_process(self.image, scale, meta, self.layout, self.color, self.matrix)
 
 
 class _PreparedSource:
@@ -109,14 +111,29 @@ PRE_DESC = np.dtype([("src_off", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W",
 FRAME_DESC = np.dtype([("base", "<u8"), ("row_stride", "<i8"), ("pix_stride", "<i8"), ("ch_off", "<i8", (3,)), ("mid_off", "<i8"),
                        ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"), ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
 
-LAYOUTS, COLORS = ("hwc", "chw"), ("bgr", "rgb")
+# cp_yuv_frame_desc (include/centerpose_hip.h): one source frame on the device in 4:2:0 YUV planes
+YUV_FRAME_DESC = np.dtype([("y_base", "<u8"), ("y_row", "<i8"), ("y_pix", "<i8"), ("u_base", "<u8"), ("v_base", "<u8"), ("c_row", "<i8"),
+                           ("c_pix", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"),
+                           ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
+
+LAYOUTS, COLORS, YUV_COLORS = ("hwc", "chw"), ("bgr", "rgb"), ("nv12", "nv21", "i420")
+
+# limited-range YUV -> BGR matrices (csrc/yuv_arith.h): (CY, CVR, CVG, CUG, CUB, YOFF), every entry round(k * 2^20)
+YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026, 16),       # 1.164, 1.596, -0.813, -0.391, 2.018
+                "bt709": (1220542, 1880097, -558891, -223347, 2214593, 16)}       # 1.164, 1.793, -0.533, -0.213, 2.112
 
 
-def _check_layout(layout, color):
+def _check_layout(layout, color, matrix="bt601"):
     if layout not in LAYOUTS:
         raise _lib.CenterposeHipError("unknown layout %r: one of %s" % (layout, ", ".join(LAYOUTS)))
-    if color not in COLORS:
-        raise _lib.CenterposeHipError("unknown color %r: one of %s" % (color, ", ".join(COLORS)))
+    if color not in COLORS + YUV_COLORS:
+        raise _lib.CenterposeHipError("unknown color %r: one of %s" % (color, ", ".join(COLORS + YUV_COLORS)))
+    if matrix not in YUV_MATRICES:
+        raise _lib.CenterposeHipError("unknown matrix %r: one of %s" % (matrix, ", ".join(sorted(YUV_MATRICES))))
+    if color in YUV_COLORS and layout != "hwc":
+        raise _lib.CenterposeHipError("layout=%r does not apply to color=%r: YUV frames are given as planes" % (layout, color))
+    if color not in YUV_COLORS and matrix != "bt601":
+        raise _lib.CenterposeHipError("matrix=%r applies to YUV frames (color %s) only, not to color=%r" % (matrix, " / ".join(YUV_COLORS), color))
 
 
 def frame_geometry(shape, strides, layout="hwc", color="bgr"):
@@ -125,6 +142,8 @@ def frame_geometry(shape, strides, layout="hwc", color="bgr"):
     element.  layout "hwc": [H,W,C], "chw": [C,H,W]; C = 3 or 4 (a fourth channel is never read); color: the order of the first three
     channels in memory.  A pure function of its arguments: nothing is copied, any strides (crops, padded rows, expanded views) go."""
     _check_layout(layout, color)
+    if color in YUV_COLORS:
+        raise _lib.CenterposeHipError("color=%r frames are planes: yuv_frame_geometry" % color)
     shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
     if len(shape) != 3 or len(strides) != 3:
         raise _lib.CenterposeHipError("a frame is 3-D ([H,W,C] or [C,H,W]), got shape %s" % (shape,))
@@ -136,6 +155,67 @@ def frame_geometry(shape, strides, layout="hwc", color="bgr"):
     if min(sh, sw, sc) < 0:
         raise _lib.CenterposeHipError("negative strides %s are not addressable" % (strides,))
     return H, W, sh, sw, ((0, sc, 2 * sc) if color == "bgr" else (2 * sc, sc, 0))
+
+
+def yuv_frame_geometry(shapes, strides, color="nv12", dtypes=None):
+    """How a 4:2:0 YUV frame given as uint8 planes is addressed.  shapes / strides (in elements == bytes): one entry per tensor of the
+    frame -- (y [H,W], uv [ceil(H/2),ceil(W/2),2]) for "nv12" / "nv21", (y, u, v) with u, v [ceil(H/2),ceil(W/2)] of equal strides for
+    "i420", or ONE 2-D surface [H*3/2, W] (H, W even, any row stride: the decoder's layout, chroma rows below the luma rows) for
+    "nv12" / "nv21"; dtypes: the tensors' dtypes when known (anything but uint8 raises).
+    -> (H, W, y_row, y_pix, u_off, v_off, c_row, c_pix): Y(r, c) at byte r * y_row + c * y_pix of the first tensor, U(r, c) at byte
+    u_off + (r >> 1) * c_row + (c >> 1) * c_pix of the tensor that holds it, V(r, c) the same from v_off (the surface itself, the uv
+    plane, or the u and the v plane, each from its own first element).  A pure function of its arguments: nothing is copied, any
+    non-negative strides (pitched rows, crops at even origins, expanded planes) go."""
+    _check_layout("hwc", color)
+    if color not in YUV_COLORS:
+        raise _lib.CenterposeHipError("color=%r frames are not planes: frame_geometry" % color)
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    strides = [tuple(int(v) for v in s) for s in strides]
+    if len(shapes) != len(strides) or any(len(a) != len(b) for a, b in zip(shapes, strides)):
+        raise _lib.CenterposeHipError("one stride per dimension of every plane: shapes %s, strides %s" % (shapes, strides))
+    for dt in (dtypes or ()):
+        if dt is not torch.uint8 and (isinstance(dt, torch.dtype) or np.dtype(dt) != np.uint8):
+            raise _lib.CenterposeHipError("the planes of a YUV frame must be uint8 (got %s)" % (dt,))
+    if any(v < 0 for s in strides for v in s):
+        raise _lib.CenterposeHipError("negative strides %s are not addressable" % (strides,))
+    if len(shapes) == 1:                                       # the decoder's surface: luma rows, then the interleaved chroma rows
+        if color == "i420":
+            raise _lib.CenterposeHipError("an i420 frame is three planes (y, u, v); one surface tensor is nv12 / nv21")
+        if len(shapes[0]) != 2:
+            raise _lib.CenterposeHipError("a %s surface is one 2-D tensor [H*3/2, W], got shape %s" % (color, shapes[0]))
+        (rows, W), (pitch, pix) = shapes[0], strides[0]
+        H = rows * 2 // 3
+        if rows <= 0 or W <= 0:
+            raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shapes[0],))
+        if rows % 3 or H % 2 or W % 2:
+            raise _lib.CenterposeHipError("a %s surface [H*3/2, W] needs even H and W, got shape %s: pass the planes (y, uv) otherwise"
+                                          % (color, shapes[0]))
+        first = H * pitch                                      # t[H:].unflatten(1, (W // 2, 2)): strides (pitch, 2 * pix, pix)
+        u_off, v_off = (first, first + pix) if color == "nv12" else (first + pix, first)
+        return H, W, pitch, pix, u_off, v_off, pitch, 2 * pix
+    want = 2 if color in ("nv12", "nv21") else 3
+    if len(shapes) != want:
+        raise _lib.CenterposeHipError("a %s frame is %s, got %d tensors" % (color, "(y, uv) or one surface" if want == 2 else "(y, u, v)",
+                                                                          len(shapes)))
+    if len(shapes[0]) != 2:
+        raise _lib.CenterposeHipError("the y plane is 2-D [H,W], got shape %s" % (shapes[0],))
+    H, W = shapes[0]
+    if H <= 0 or W <= 0:
+        raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shapes[0],))
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    if want == 2:
+        if shapes[1] != (ch, cw, 2):
+            raise _lib.CenterposeHipError("the uv plane of a %d x %d %s frame is [%d,%d,2], got shape %s" % (H, W, color, ch, cw, shapes[1]))
+        c_row, c_pix, sc = strides[1]
+        u_off, v_off = (0, sc) if color == "nv12" else (sc, 0)
+    else:
+        if shapes[1] != (ch, cw) or shapes[2] != (ch, cw):
+            raise _lib.CenterposeHipError("the u and v planes of a %d x %d i420 frame are [%d,%d], got shapes %s and %s"
+                                          % (H, W, ch, cw, shapes[1], shapes[2]))
+        if strides[1] != strides[2]:
+            raise _lib.CenterposeHipError("the u and v planes must have equal strides (%s and %s)" % (strides[1], strides[2]))
+        (c_row, c_pix), u_off, v_off = strides[1], 0, 0
+    return H, W, strides[0][0], strides[0][1], u_off, v_off, c_row, c_pix
 
 
 class _Staging:
@@ -223,13 +303,19 @@ class BaseDetector(object):
         return (new_h, new_w, inp_h, inp_w, np.array([new_w // 2, new_h // 2], dtype=np.float32),
                 np.array([inp_w, inp_h], dtype=np.float32))
 
-    def pre_process(self, image, scale, meta=None, layout="hwc", color="bgr"):
+    def pre_process(self, image, scale, meta=None, layout="hwc", color="bgr", matrix="bt601"):
         """base_detector.py:32-62.  image: HxWx3 uint8 BGR host array -> (images float32 [1 or 2,3,inp_h,inp_w] ON THE
         DEVICE, meta).  cv2.resize + cv2.warpAffine + normalise + transpose (+ flipped twin) run as HIP kernels.
         image may also be one frame that is already on the device: a CUDA uint8 tensor [H,W,C] (layout="hwc") or [C,H,W] ("chw"),
         C = 3 or 4, channels in memory in `color` order ("bgr" / "rgb"), any strides.  It is read in place (no copy, no upload) by
         pre_process_batch's device path, whose stream-order and lifetime rules apply; the result is bit-identical to the same call
-        on the equivalent HxWx3 BGR host array.  Host arrays are cv2's layout: another layout / color raises for them."""
+        on the equivalent HxWx3 BGR host array.  Host arrays are cv2's layout: another layout / color raises for them.
+        color "nv12" / "nv21" / "i420": image is one 4:2:0 YUV frame on the device (a tuple of plane tensors or, for nv12 / nv21, one
+        surface tensor), converted with `matrix` ("bt601" / "bt709") -- see pre_process_batch."""
+        _check_layout(layout, color, matrix)
+        if color in YUV_COLORS:
+            x, metas = self.pre_process_batch([image], scale, layout, color, matrix)
+            return x, metas[0]
         if isinstance(image, torch.Tensor):
             if image.dim() != 3:
                 raise _lib.CenterposeHipError("pre_process takes one 3-D frame tensor, got shape %s (N frames: pre_process_batch)"
@@ -286,8 +372,8 @@ class BaseDetector(object):
         return images
 
     @staticmethod
-    def _host_layout_only(layout, color):
-        _check_layout(layout, color)      # unknown names raise
+    def _host_layout_only(layout, color, matrix="bt601"):
+        _check_layout(layout, color, matrix)      # unknown names raise
         if (layout, color) != ("hwc", "bgr"):
             raise _lib.CenterposeHipError("host arrays are taken in cv2's layout (HxWx3, BGR): layout=%r / color=%r apply to frames "
                                           "on the device (CUDA uint8 tensors) only" % (layout, color))
@@ -311,10 +397,46 @@ class BaseDetector(object):
             raise _lib.CenterposeHipError("a frame tensor on %s, the model is on %s" % (t.device, device))
         return (t.data_ptr(),) + geometry
 
-    def _batch_input(self, images, layout, color):
+    def _yuv_frame(self, frame, color):
+        """One device frame in 4:2:0 YUV -> (address of Y(0,0), H, W, y_row, y_pix, address of U(0,0), address of V(0,0), c_row, c_pix),
+        all from the plane tensors' own shapes, strides and data pointers.  One 2-D surface tensor (nv12 / nv21) is split into the views
+        t[:H] and t[H:].unflatten(1, (W // 2, 2)) by address alone.  Nothing is copied or made contiguous."""
+        planes = [frame] if isinstance(frame, (torch.Tensor, np.ndarray)) else list(frame)
+        if not planes:
+            raise _lib.CenterposeHipError("a %s frame without planes" % color)
+        if any(isinstance(t, np.ndarray) for t in planes):
+            if all(isinstance(t, np.ndarray) for t in planes):
+                raise _lib.CenterposeHipError("host arrays are taken in cv2's layout (HxWx3, BGR): color=%r applies to frames on the "
+                                              "device (CUDA uint8 plane tensors) only" % color)
+            raise _lib.CenterposeHipError("host arrays and device tensors mixed in one frame: pass all planes as CUDA tensors")
+        if not all(isinstance(t, torch.Tensor) for t in planes):
+            raise _lib.CenterposeHipError("a %s frame is a tuple of CUDA uint8 plane tensors (or one surface tensor for nv12 / nv21)" % color)
+        for t in planes:
+            if not t.is_cuda:
+                raise _lib.CenterposeHipError("a plane tensor on %s: the planes of a frame must be on the model's GPU; there is no host "
+                                              "fallback" % t.device)
+        H, W, y_row, y_pix, u_off, v_off, c_row, c_pix = yuv_frame_geometry([t.shape for t in planes], [t.stride() for t in planes], color,
+                                                                            [t.dtype for t in planes])
+        device = self._model_device()
+        for t in planes:
+            if t.device != device:
+                raise _lib.CenterposeHipError("a plane tensor on %s, the model is on %s" % (t.device, device))
+        u_plane, v_plane = (planes[0], planes[0]) if len(planes) == 1 else (planes[1], planes[-1])
+        return (planes[0].data_ptr(), H, W, y_row, y_pix, u_plane.data_ptr() + u_off, v_plane.data_ptr() + v_off, c_row, c_pix)
+
+    def _batch_input(self, images, layout, color, matrix="bt601"):
         """What a batched call was given -> (images as a list, frames): frames is None for host arrays (the staging path), else one
-        `_frame` per device tensor.  One 4-D tensor means N frames ([N,H,W,C] or [N,C,H,W])."""
-        _check_layout(layout, color)      # unknown names raise, whatever the input
+        `_frame` per device tensor (`_yuv_frame` per frame with a YUV color).  One 4-D tensor means N frames ([N,H,W,C] or [N,C,H,W])."""
+        _check_layout(layout, color, matrix)      # unknown names raise, whatever the input
+        if color in YUV_COLORS:
+            if isinstance(images, (torch.Tensor, np.ndarray)):
+                raise _lib.CenterposeHipError("a batch of %s frames is a list of frames (plane tuples or surface tensors), got one %s of "
+                                              "shape %s" % (color, type(images).__name__, tuple(images.shape)))
+            images = list(images)
+            host = sum(isinstance(im, np.ndarray) for im in images)
+            if 0 < host < len(images):
+                raise _lib.CenterposeHipError("host arrays and device tensors mixed in one call: pass all frames one way")
+            return images, [self._yuv_frame(im, color) for im in images]
         if isinstance(images, torch.Tensor):
             if images.dim() != 4:
                 raise _lib.CenterposeHipError("one tensor for N frames is 4-D ([N,H,W,C] or [N,C,H,W]), got shape %s; pass a list of "
@@ -348,13 +470,14 @@ class BaseDetector(object):
             groups.setdefault(key, []).append(i)
         return list(groups.values())
 
-    def _pre_table(self, shapes, offsets, idx, scale, frames=None):
+    def _pre_table(self, shapes, offsets, idx, scale, frames=None, yuv=False):
         """The descriptor table of one batched pre-process: images `idx` at `scale`, which must share one network input shape
         -> (table, scratch_bytes, inp_h, inp_w, metas).  Geometry, matrix and meta per image are pre_process's.  PRE_DESC rows with the
-        images' staging `offsets`, or, with `frames` (`_frame` per image), FRAME_DESC rows that address the frames where they lie."""
+        images' staging `offsets`, or, with `frames` (`_frame` per image), FRAME_DESC rows that address the frames where they lie
+        (`yuv`: `_yuv_frame` per image, YUV_FRAME_DESC rows)."""
         nb = 2 if self.cfg.TEST.FLIP_TEST else 1
         down = self.cfg.MODEL.DOWN_RATIO
-        table = np.zeros(len(idx), PRE_DESC if frames is None else FRAME_DESC)
+        table = np.zeros(len(idx), PRE_DESC if frames is None else (YUV_FRAME_DESC if yuv else FRAME_DESC))
         metas, scratch, inp = [], 0, None
         for j, i in enumerate(idx):
             height, width = shapes[i]
@@ -370,6 +493,8 @@ class BaseDetector(object):
             d["H"], d["W"], d["NH"], d["NW"], d["slot"] = height, width, new_h, new_w, nb * j
             if frames is None:
                 d["src_off"] = offsets[i]
+            elif yuv:
+                d["y_base"], _, _, d["y_row"], d["y_pix"], d["u_base"], d["v_base"], d["c_row"], d["c_pix"] = frames[i]
             else:
                 d["base"], _, _, d["row_stride"], d["pix_stride"], d["ch_off"] = frames[i]
             if (new_h, new_w) != (height, width):
@@ -430,9 +555,17 @@ class BaseDetector(object):
         std = np.ascontiguousarray(self.std.reshape(3), np.float32)
         return nb, n, x, scratch, mean, std, np.ascontiguousarray(table)
 
-    def _launch_frames(self, table_dev, table, scratch_bytes, inp_h, inp_w):
-        """cp_preprocess_frames_u8_f32 for one FRAME_DESC table -> float32 [nb * N, 3, inp_h, inp_w] on the device."""
+    def _launch_frames(self, table_dev, table, scratch_bytes, inp_h, inp_w, coef=None):
+        """cp_preprocess_frames_u8_f32 for one FRAME_DESC table -> float32 [nb * N, 3, inp_h, inp_w] on the device.  With `coef` (six
+        ints, YUV_MATRICES): cp_preprocess_yuv_frames_u8_f32 for one YUV_FRAME_DESC table."""
         nb, n, x, scratch, mean, std, table = self._pre_buffers(table, scratch_bytes, inp_h, inp_w)
+        if coef is not None:
+            rc = _lib.lib().cp_preprocess_yuv_frames_u8_f32(
+                ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, (ctypes.c_int * 6)(*coef),
+                ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch_bytes), _lib.ptr(x), nb * n, inp_h, inp_w,
+                mean.ctypes.data_as(ctypes.c_void_p), std.ctypes.data_as(ctypes.c_void_p), 1 if nb == 2 else 0, _lib.stream())
+            _lib.check(rc, "cp_preprocess_yuv_frames_u8_f32")
+            return x
         rc = _lib.lib().cp_preprocess_frames_u8_f32(
             ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, ctypes.c_void_p(scratch.data_ptr()),
             ctypes.c_size_t(scratch_bytes), _lib.ptr(x), nb * n, inp_h, inp_w, mean.ctypes.data_as(ctypes.c_void_p),
@@ -440,7 +573,7 @@ class BaseDetector(object):
         _lib.check(rc, "cp_preprocess_frames_u8_f32")
         return x
 
-    def pre_process_batch(self, images, scale, layout="hwc", color="bgr"):
+    def pre_process_batch(self, images, scale, layout="hwc", color="bgr", matrix="bt601"):
         """pre_process for N images that share one network input shape at `scale` (any sizes with FIX_RES) -> (float32
         [nb * N, 3, inp_h, inp_w] ON THE DEVICE, list of N meta dicts); nb = 2 with FLIP_TEST: image n at 2n, its mirrored twin at
         2n + 1, the layout `process` takes.  One upload of the images, one of the descriptor table, one resize launch (if any image
@@ -451,15 +584,24 @@ class BaseDetector(object):
         staging copy and no `.contiguous()`; bit-identical to the call on the equivalent HxWx3 BGR host arrays.  The launches go to
         the current stream: whatever produced the frames must be ordered before this call on that stream, and a frame must stay
         allocated until the launches have run -- a tensor that was allocated on another stream needs `record_stream` for the
-        current one before it is released.  Host arrays and tensors cannot be mixed; host arrays take layout / color defaults only."""
-        images, frames = self._batch_input(images, layout, color)
+        current one before it is released.  Host arrays and tensors cannot be mixed; host arrays take layout / color defaults only.
+        Frames in 4:2:0 YUV: color "nv12" / "nv21" / "i420" (layout stays the default), `images` a list of frames, each a tuple of CUDA
+        uint8 plane tensors -- (y [H,W], uv [ceil(H/2),ceil(W/2),2]) for nv12 (uv[..., 0] is U) and nv21 (uv[..., 0] is V), (y, u, v)
+        with u, v [ceil(H/2),ceil(W/2)] of equal strides for i420 (YV12 is i420 with the planes passed in (y, u, v) order, i.e. the
+        file's third plane second) -- or, for nv12 / nv21, one 2-D tensor [H*3/2, W] with even H, W and any row stride: a decoder's
+        surface, split into its plane views here.  Any strides; nothing is copied.  cp_preprocess_yuv_frames_u8_f32 converts every
+        pixel to BGR where it is loaded, with the limited-range `matrix` "bt601" (cv2's COLOR_YUV2BGR_NV12 arithmetic) or "bt709",
+        nearest chroma: bit-identical to the call on the HxWx3 BGR host array that conversion gives (csrc/yuv_arith.h).  The
+        stream-order and lifetime rules above hold for every plane.  Host YUV arrays are not taken."""
+        images, frames = self._batch_input(images, layout, color, matrix)
         if not images:
             raise _lib.CenterposeHipError("pre_process_batch needs at least one image")
         if frames is not None:
             shapes = [f[1:3] for f in frames]
-            table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, None, list(range(len(frames))), scale, frames)
+            coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+            table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, None, list(range(len(frames))), scale, frames, coef is not None)
             table_dev, = self._upload_table([table])
-            return self._launch_frames(table_dev, table, scratch_bytes, inp_h, inp_w), metas
+            return self._launch_frames(table_dev, table, scratch_bytes, inp_h, inp_w, coef), metas
         shapes = [im.shape[0:2] for im in images]
         offsets, nbytes = self._batch_layout(shapes)
         table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale)
@@ -479,7 +621,7 @@ class BaseDetector(object):
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False):
+    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601"):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -490,10 +632,13 @@ class BaseDetector(object):
         ValueError where `process_dets` raises it.
         Frames on the device: `images` as for pre_process_batch (a list of CUDA uint8 tensors or one 4-D tensor, `layout`, `color`);
         they are read in place, the descriptor tables are the call's only upload, and the results equal those of the same frames
-        given as host arrays.  The same stream-order and lifetime rules hold.
+        given as host arrays.  The same stream-order and lifetime rules hold.  Frames in 4:2:0 YUV (color "nv12" / "nv21" / "i420",
+        `matrix`): a list of plane tuples or surface tensors as for pre_process_batch, the rules per plane; the results equal those of
+        the converted BGR host arrays.
         return_device=True (host or device input): the rows as ONE device tensor float32 [N, S*K, 56] in input order instead of the
         list -- no download and no synchronisation; the tensor is ready in the current stream's order."""
-        images, frames = self._batch_input(images, layout, color)
+        images, frames = self._batch_input(images, layout, color, matrix)
+        coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
         if not images:
             return torch.empty((0, 0, 56), dtype=torch.float32, device="cuda") if return_device else []
         shapes = [im.shape[0:2] for im in images] if frames is None else [f[1:3] for f in frames]
@@ -502,7 +647,7 @@ class BaseDetector(object):
         work, parts = [], []
         for idx in groups:
             for scale in self.scales:
-                table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, idx, scale, frames)
+                table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, idx, scale, frames, coef is not None)
                 work.append((table, scratch_bytes, inp_h, inp_w))
                 parts += [table, self._inverse_affines(metas)]
         order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
@@ -519,7 +664,7 @@ class BaseDetector(object):
                 if frames is None:
                     x = self._launch_pre(staging, parts[2 * j], table, scratch_bytes, inp_h, inp_w)
                 else:
-                    x = self._launch_frames(parts[2 * j], table, scratch_bytes, inp_h, inp_w)
+                    x = self._launch_frames(parts[2 * j], table, scratch_bytes, inp_h, inp_w, coef)
                 dets = self.process_dets(x) if dets_only else self._process_batch(x)
                 per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
             merged.append(self.merge_outputs_batch(per_scale))
@@ -532,20 +677,22 @@ class BaseDetector(object):
             results[i] = {1: rows[r].tolist()}
         return results
 
-    def _source(self, x, layout="hwc", color="bgr"):
-        if isinstance(x, (np.ndarray, torch.Tensor)):
-            return _ArraySource(x, layout, color)
+    def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):
+        if isinstance(x, (np.ndarray, torch.Tensor)) or (color in YUV_COLORS and isinstance(x, (tuple, list))):
+            return _ArraySource(x, layout, color, matrix)
         if isinstance(x, str):
-            return _ArraySource(_imread(x), layout, color)
+            return _ArraySource(_imread(x), layout, color, matrix)
         return _PreparedSource(x)
 
-    def run(self, image_or_path_or_tensor, meta=None, layout="hwc", color="bgr"):
+    def run(self, image_or_path_or_tensor, meta=None, layout="hwc", color="bgr", matrix="bt601"):
         """base_detector.py:79-140: every TEST_SCALES entry through pre_process -> process -> post_process, then
         merge_outputs; returns {'results': {1: rows}, 'tot', 'load', 'pre', 'net', 'dec', 'post', 'merge'}.
         A CUDA uint8 tensor is one frame on the device in the given `layout` / `color` (see pre_process): read in place, same results
-        as the equivalent host array."""
+        as the equivalent host array.  With color "nv12" / "nv21" / "i420": one 4:2:0 YUV frame on the device (plane tuple or surface
+        tensor, `matrix`), as for pre_process."""
+        _check_layout(layout, color, matrix)
         clock = StageClock(torch.cuda.synchronize)
-        source = self._source(image_or_path_or_tensor, layout, color)
+        source = self._source(image_or_path_or_tensor, layout, color, matrix)
         clock.lap("load", sync=False)
         per_scale = []
         for scale in self.scales:

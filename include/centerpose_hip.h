@@ -8,7 +8,8 @@
  * are enqueued on `stream` only (so a caller may capture a sequence of calls into a hipGraph).  The plan handle
  * (cp_plan_*) is the one exception and says so.
  * Source images reach the pre-process either through one staging buffer (cp_pre_desc) or, when they are on the device already, in
- * place through a per-frame address and strides (cp_frame_desc); both are read when `stream` reaches the launches.
+ * place through a per-frame address and strides (cp_frame_desc; cp_yuv_frame_desc for 4:2:0 YUV planes, converted to BGR where the
+ * pixels are loaded); all are read when `stream` reaches the launches.
  *
  * File:line citations are relative to the reference checkout (/root/reference).
  * Activation layout: NHWC float32, `ld` = floats between consecutive pixels (>= C).
@@ -393,6 +394,48 @@ typedef struct cp_frame_desc {      /* 128 bytes */
 int cp_sizeof_frame_desc(void);
 int cp_preprocess_frames_u8_f32(const void* table, const void* table_host, int N, unsigned char* scratch, size_t scratch_bytes,
                                 float* out, int out_batch, int OH, int OW, const float* mean, const float* std_, int flip, void* stream);
+
+/* ---- the same from device frames in 4:2:0 YUV: NV12 (a hardware decoder's surface), NV21, I420 / YV12 -----------------------------
+ * cp_yuv_frame_desc: one source frame of 8-bit planes, read IN PLACE.  Y(r, c) is the byte at y_base + r * y_row + c * y_pix, U(r, c)
+ *   the byte at u_base + (r >> 1) * c_row + (c >> 1) * c_pix, V(r, c) the same expression from v_base: the chroma of a pixel is the
+ *   nearest sample, one (U, V) pair per 2x2 block, no chroma interpolation.  NV12: v_base = u_base + 1, c_pix = 2; NV21: u_base =
+ *   v_base + 1, c_pix = 2; I420 / YV12: two chroma planes, c_pix = 1.  Pitched rows, crops at even origins and expanded planes (a
+ *   stride of 0) are the same rule; H or W may be odd, the chroma planes then hold (H + 1) / 2 x (W + 1) / 2 samples.  mid_off, H, W,
+ *   NH, NW, mi, slot: as in cp_frame_desc; the resized intermediate is packed [NH,NW,3] BGR.
+ * The conversion (csrc/yuv_arith.h) is integer-only.  coef = (CY, CVR, CVG, CUG, CUB, YOFF), HOST int[6]; in int32, arithmetic shifts:
+ *       y = max(Y - YOFF, 0) * CY;  u = U - 128;  v = V - 128
+ *       R = clamp((y + CVR * v + (1 << 19)) >> 20, 0, 255)
+ *       G = clamp((y + CVG * v + CUG * u + (1 << 19)) >> 20, 0, 255)
+ *       B = clamp((y + CUB * u + (1 << 19)) >> 20, 0, 255)
+ *   limited-range BT.601: (1220542, 1673527, -852492, -409993, 2116026, 16) -- the constants, rounding term and shift of
+ *   cv2.cvtColor(COLOR_YUV2BGR_NV12), restated, not pinned to a recording; limited-range BT.709: (1220542, 1880097, -558891, -223347,
+ *   2214593, 16).  Any other matrix goes if it cannot overflow int32: CY > 0, 0 <= YOFF <= 255 and
+ *   255 * CY + (1 << 19) + 128 * max(|CVR|, |CVG| + |CUG|, |CUB|) < 2^31; anything else is an argument error.
+ * cp_preprocess_yuv_frames_u8_f32: cp_preprocess_frames_u8_f32 for such frames: one resize launch (when any frame has mid_off >= 0) and
+ *   one warp launch, bit-identical to cp_preprocess_frames_u8_f32 on the packed [H,W,3] BGR image obtained by converting every pixel of
+ *   the frame (per source pixel, before the resize and before the warp).  table: DEVICE cp_yuv_frame_desc[N], table_host: the same
+ *   descriptors on the HOST, checked before anything is launched: the three bases non-null, sizes positive and below 2^29 pixels,
+ *   strides >= 0, every plane's largest addressed offset below 2^62, mid_off / scratch / slot as for cp_preprocess_frames_u8_f32,
+ *   N <= 65535, and coef as above.  The caller vouches for the planes' memory, stream order and lifetime exactly as for cp_frame_desc,
+ *   per plane.  cp_last_kernel(): preprocess_yuv_frames_kernel<vec4|scalar>.
+ * cp_yuv_to_bgr_host: HOST only -- the conversion of n (Y, U, V) triples to bgr[3 * n] by the same statements the kernels compile. */
+typedef struct cp_yuv_frame_desc {  /* 136 bytes */
+    const unsigned char* y_base;    /* DEVICE address of Y(0,0) */
+    long long y_row, y_pix;         /* bytes */
+    const unsigned char* u_base;    /* DEVICE address of U(0,0) */
+    const unsigned char* v_base;    /* DEVICE address of V(0,0) */
+    long long c_row, c_pix;         /* bytes per chroma row / per chroma sample, both chroma planes */
+    long long mid_off;              /* as cp_pre_desc: offset of the resized image in scratch, < 0: no resize */
+    int H, W, NH, NW;
+    double mi[6];                   /* inverted warp matrix (cp_invert_warp) */
+    int slot, pad;
+} cp_yuv_frame_desc;
+int cp_sizeof_yuv_frame_desc(void);
+int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* table_host, int N, const int* coef, unsigned char* scratch,
+                                    size_t scratch_bytes, float* out, int out_batch, int OH, int OW, const float* mean, const float* std_,
+                                    int flip, void* stream);
+int cp_yuv_to_bgr_host(const unsigned char* y, const unsigned char* u, const unsigned char* v, size_t n, const int* coef,
+                       unsigned char* bgr);
 
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
