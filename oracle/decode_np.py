@@ -108,6 +108,7 @@ def multi_pose_decode(heat, wh, kps, reg=None, hm_hp=None, hp_offset=None, K=100
     else:
         hm_xs = hm_xs + F32(0.5)
         hm_ys = hm_ys + F32(0.5)
+    raw_score = hm_score
     mask = (hm_score > thresh).astype(F32)                        # :282
     hm_score = (F32(1) - mask) * F32(-1) + mask * hm_score        # :283
     hm_ys = (F32(1) - mask) * F32(-10000) + mask * hm_ys          # :284
@@ -136,8 +137,16 @@ def multi_pose_decode(heat, wh, kps, reg=None, hm_hp=None, hp_offset=None, K=100
                            np.ascontiguousarray(sel_score[..., 0].transpose(0, 2, 1))],
                           axis=2).astype(F32)                      # :307
     if return_aux:
-        return dets, {"inds": inds, "hm_inds": hm_inds, "scores": scores,
-                      "hm_score_topk": topk_channel(hm_hp, K)[0]}
+        # the operands of every comparison of :282 and :300-302, [B,J,K] (cand_* : per candidate m; the rest per centre k)
+        sq = lambda a: a[..., 0]
+        cmp = {"cand_score": raw_score, "cand_x": hm_xs, "cand_y": hm_ys, "cand_s": hm_score, "dist": dist, "min_ind": min_ind,
+               "sel_x": sq(sel_x), "sel_y": sq(sel_y), "sel_score": sq(sel_score), "min_dist": sq(min_dist),
+               "l": np.broadcast_to(sq(l), min_ind.shape), "t": np.broadcast_to(sq(t), min_ind.shape),
+               "r": np.broadcast_to(sq(r_), min_ind.shape), "b": np.broadcast_to(sq(b_), min_ind.shape),
+               "limit": np.broadcast_to(sq(np.maximum(b_ - t, r_ - l) * F32(0.3)), min_ind.shape), "rej": sq(rej),
+               "kp_x": kpj[..., 0], "kp_y": kpj[..., 1]}
+        return dets, {"inds": inds, "hm_inds": hm_inds, "scores": scores, "clses": clses,
+                      "hm_score_topk": topk_channel(hm_hp, K)[0], "cmp": cmp}
     return dets
 
 

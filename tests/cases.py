@@ -417,3 +417,227 @@ def dcn_fixtures():
     for row in DCN_LATTICE_CONFIGS:
         fx["lattice_" + row[0]] = (lambda row=row: dcn_lattice_case(*row))
     return fx
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Decode decisions at their limits (tests/test_decode_edges_*.py, tests/golden/make_golden.py decode_edges).
+#
+# Every scene is built from dyadic values, so that the arithmetic of the reference's multi_pose_decode (decode.py:244-304) is exact
+# and the side of each comparison is known by construction (and asserted here).  A TRIPLET is one scene three times: the moving
+# operand one float32 below its limit (side -1), exactly on it (0) and one float32 above (+1).  The comparisons:
+ASSIGN_COMPARISONS = ("sx<l", "sx>r", "sy<t", "sy>b", "ss<0.1", "best>lim", "s>0.1")
+
+
+def _next(v, up):
+    return F32(np.nextafter(F32(v), F32(np.inf if up else -np.inf)))
+
+
+def _around(v):
+    """side -> the float32 below / on / above v."""
+    return {-1: _next(v, False), 0: F32(v), 1: _next(v, True)}
+
+
+def _exact_sum(a, b):
+    """float32(a) + float32(b) in float32, asserted exact."""
+    s = F32(a) + F32(b)
+    assert float(s) == float(F32(a)) + float(F32(b)), (a, b)
+    return s
+
+
+def _fillers(H, W, n):
+    pos = [(y, x) for y in (H - 2, 2) for x in range(W - 2, 0, -4)]
+    assert len(pos) >= n
+    return pos[:n]
+
+
+def edge_scene(H=16, W=16, K=4, centre=(8, 8), wh=(8.0, 8.0), reg=(0.0, 0.0), joints=()):
+    """One image.  Centre plane: the main centre (score 0.5, rank 0) and K + 2 lower, distinct fillers far from it, so that the
+    top-(K+1) of the plane has no tie.  joints: per joint (hps_x, hps_y, [(y, x, score, off_x, off_y), ...]) -- hps / wh / reg are
+    constant maps, hp_offset is zero but at the candidates; each joint plane gets K + 2 distinct fillers of at most 1/16 (under the
+    0.1 threshold: -1 / -10000 sentinels)."""
+    J = len(joints)
+    hm = np.zeros((1, 1, H, W), F32)
+    hm_hp = np.zeros((1, J, H, W), F32)
+    hps = np.zeros((1, 2 * J, H, W), F32)
+    off = np.zeros((1, 2, H, W), F32)
+    hm[0, 0, centre[0], centre[1]] = 0.5
+    fill = _fillers(H, W, K + 2)
+    for i, (y, x) in enumerate(fill):
+        assert abs(y - centre[0]) > 1
+        hm[0, 0, y, x] = (16 - i) / 64.0
+    for j, (hx, hy, cands) in enumerate(joints):
+        hps[0, 2 * j], hps[0, 2 * j + 1] = hx, hy
+        for i, (y, x) in enumerate(fill):
+            hm_hp[0, j, y, x] = (16 - i) / 256.0
+        for (y, x, s, ox, oy) in cands:
+            assert min(abs(y - fy) for fy, _ in fill) > 1 and hm_hp[0, j, y, x] == 0
+            hm_hp[0, j, y, x] = s
+            assert (off[0, :, y, x] == 0).all() or (off[0, 0, y, x] == F32(ox) and off[0, 1, y, x] == F32(oy))
+            off[0, 0, y, x], off[0, 1, y, x] = ox, oy
+    whm = np.empty((1, 2, H, W), F32)
+    whm[0, 0], whm[0, 1] = wh
+    regm = np.empty((1, 2, H, W), F32)
+    regm[0, 0], regm[0, 1] = reg
+    return dict(hm=hm, wh=whm, hps=hps, reg=regm, hm_hp=hm_hp, hp_offset=off)
+
+
+def _stack(*scenes):
+    return {k: np.concatenate([s[k] for s in scenes], 0) for k in scenes[0]}
+
+
+def _plain_joint(c=(8, 8)):
+    """A joint with one accepted candidate on the centre, far from every limit."""
+    return (0.25, 0.25, [(c[0], c[1], 0.75, 0.5, 0.5)])
+
+
+def decode_assign_edges():
+    """name -> dict(inp, K, use_reg, use_off, group, side, cmp, j).  group / side / cmp are None for the cases that are no triplet
+    member; the decision under test is the one of image 0, centre rank 0 (the 0.5 peak), joint j."""
+    out = {}
+
+    def add(name, inp, K=4, use_reg=True, use_off=True, group=None, side=None, cmp=None, j=0):
+        assert name not in out
+        out[name] = dict(inp=inp, K=K, use_reg=use_reg, use_off=use_off, group=group, side=side, cmp=cmp, j=j)
+
+    names = {-1: "below", 0: "at", 1: "above"}
+    # -- box edges: centre (8, 8), wh 8, reg 0 -> l = t = 4, r = b = 12; the candidate sits on the edge pixel and hp_offset moves it
+    edges = {"left": ("sx<l", 8, 4, 0, -3.75, 0.25), "right": ("sx>r", 8, 12, 0, 3.75, 0.25),
+             "top": ("sy<t", 4, 8, 1, 0.25, -3.75), "bottom": ("sy>b", 12, 8, 1, 0.25, 3.75)}
+    for ename, (cmp, y, x, axis, hx, hy) in edges.items():
+        base = (x, y)[axis]
+        for side, target in _around(base).items():
+            o = F32(float(target) - base)
+            assert _exact_sum(base, o) == target
+            cand = (y, x, 0.75, o if axis == 0 else 0.0, o if axis == 1 else 0.0)
+            if axis == 0:
+                add("%s_%s" % (ename, names[side]), edge_scene(joints=[(hx, hy, [cand])]), group=ename, side=side, cmp=cmp)
+            else:                           # two joints, the decision in the second
+                add("%s_%s" % (ename, names[side]), edge_scene(joints=[_plain_joint(), (hx, hy, [cand])]), group=ename, side=side,
+                    cmp=cmp, j=1)
+    # the right-edge triplet again as image 0 of a batch of two 32 x 32 maps with K = 8 (image 1: the top edge, exactly on it)
+    for side, target in _around(12).items():
+        o = F32(float(target) - 12)
+        im0 = edge_scene(32, 32, 8, joints=[(3.75, 0.25, [(8, 12, 0.75, o, 0.0)]), _plain_joint()])
+        im1 = edge_scene(32, 32, 8, joints=[_plain_joint(), (0.25, -3.75, [(4, 8, 0.75, 0.0, 0.0)])])
+        add("b2_right_%s" % names[side], _stack(im0, im1), K=8, group="b2_right", side=side, cmp="sx>r")
+    # -- candidate score on 0.1: the joint plane's peak (fillers <= 1/16).  Under and on 0.1 it is masked to the sentinels, and then
+    # no candidate of the plane is valid: ss = -1.  (`ss < 0.1f` never sees equal operands: ss is -1 or a score above 0.1.)
+    for side, s in _around(0.1).items():
+        add("score_%s" % names[side], edge_scene(joints=[(0.25, 0.25, [(8, 8, s, 0.0, 0.0)])]), group="score", side=side, cmp="s>0.1")
+    # the same with a second, valid candidate outside the distance limit: ss is then a score, never -1
+    for side, s in _around(0.1).items():
+        add("score2_%s" % names[side], edge_scene(joints=[(0.25, 0.25, [(8, 8, s, 0.0, 0.0), (8, 11, 0.5, 0.0, 0.0)])]),
+            group="score2", side=side, cmp="s>0.1")
+    # -- distance limit fl(8 * 0.3f): candidate at x = 1 (sx = 1), centre at x = 2, dy = 0, kx = 1 + d with d below / on / above the
+    # limit; once max(h, w) = h and once = w.  Three joints, the decision in the last.
+    lim = F32(F32(8) * F32(0.3))
+    for tag, whv in (("h", (4.0, 8.0)), ("w", (8.0, 4.0))):
+        for side, d in _around(lim).items():
+            kx = _exact_sum(1, d)
+            hx = F32(float(kx) - 2)
+            assert _exact_sum(hx, 2) == kx and F32(kx - F32(1)) == d
+            assert np.sqrt(F32(d * d) + F32(0) * F32(0), dtype=F32) == d      # the float32 distance IS d
+            sc = edge_scene(centre=(8, 2), wh=whv, joints=[_plain_joint((8, 2)), _plain_joint((8, 2)), (hx, 0.0, [(8, 1, 0.75, 0.0, 0.0)])])
+            add("dist_%s_%s" % (tag, names[side]), sc, group="dist_" + tag, side=side, cmp="best>lim", j=2)
+    # -- equal distances: candidates symmetric about the regressed point (8, 8); the first in the joint's top-K order wins
+    add("tie_left_first", edge_scene(joints=[(0.0, 0.0, [(8, 6, 0.75, 0.0, 0.0), (8, 10, 0.5, 0.0, 0.0)])]))
+    add("tie_right_first", edge_scene(joints=[(0.0, 0.0, [(8, 6, 0.5, 0.0, 0.0), (8, 10, 0.75, 0.0, 0.0)])]))
+    add("tie_three", edge_scene(joints=[(0.0, 0.0, [(8, 6, 0.5, 0.0, 0.0), (8, 10, 0.75, 0.0, 0.0), (6, 8, 0.625, 0.0, 0.0)])]))
+    # -- a joint plane without any candidate above 0.1: K equal distances to (-10000, -10000), index 0 wins, score -1
+    add("no_candidate", edge_scene(joints=[_plain_joint(), (0.25, 0.25, [])]), j=1)
+    # -- the +0.5f branches.  reg=None: cx = 8.5, l = 4.5, hp_offset moves the candidate of pixel x = 4 through it
+    for side, target in _around(4.5).items():
+        o = F32(float(target) - 4)
+        assert _exact_sum(4, o) == target
+        add("noreg_left_%s" % names[side], edge_scene(joints=[(-3.25, 0.25, [(8, 4, 0.75, o, 0.0)])]), use_reg=False,
+            group="noreg_left", side=side, cmp="sx<l")
+    # reg=None and hp_offset=None: sx = 4.5 stays, wh moves l = 8.5 - w / 2 through it (side: sx relative to l)
+    for side, lt in ((-1, _next(4.5, True)), (0, F32(4.5)), (1, _next(4.5, False))):
+        w = F32(2 * (8.5 - float(lt)))
+        assert F32(F32(8.5) - w / F32(2)) == lt and float(w) == 2 * (8.5 - float(lt))
+        add("nooff_left_%s" % names[side], edge_scene(wh=(w, 8.0), joints=[(-3.25, 0.75, [(8, 4, 0.75, 0.0, 0.0)])]), use_reg=False,
+            use_off=False, group="nooff_left", side=side, cmp="sx<l")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# More than one centre class.  name -> (cat, H, W, K, J, seed, seam)
+DECODE_MULTICAT_CASES = {
+    "cat4_64x64": (4, 64, 64, 100, 2, 501, False),         # 16 384 keys: register path, power-of-two index math across planes
+    "cat3_32x48": (3, 32, 48, 40, 2, 502, False),          # register path, division index math
+    "cat2_15x17": (2, 15, 17, 9, 2, 503, False),           # planes not 16-byte aligned
+    "cat2_128x96": (2, 128, 96, 100, 2, 504, False),       # 24 576 keys: LDS path without registers
+    "cat3_128x128": (3, 128, 128, 100, 2, 505, False),     # 49 152 keys: 2 chunks of 24 576, the first ends inside plane 1
+    "cat5_100x131": (5, 100, 131, 256, 2, 506, False),     # 65 500 keys: 2 odd chunks, neither boundary on a map row
+    "seam_cat4_64x64": (4, 64, 64, 100, 1, 511, True),
+    "seam_cat2_15x17": (2, 15, 17, 9, 1, 512, True),
+    "seam_cat2_128x96": (2, 128, 96, 100, 1, 513, True),
+    "seam_cat3_128x128": (3, 128, 128, 100, 1, 514, True),
+}
+
+
+def seam_peaks(cat, H, W):
+    """(class, y, x, value) of the peaks the seam cases plant beside a plane boundary; NMS has to keep every one."""
+    out = []
+    for c in range(cat - 1):
+        out.append((c, H - 1, 5, 2.0 + c / 16.0))            # last row of plane c; larger values follow it in memory
+        out.append((c + 1, 0, W - 6, 2.5 + c / 16.0))        # row 0 of plane c + 1; larger values precede it in memory
+    return out
+
+
+def decode_multicat(cat, H, W, J, seed, seam=False):
+    r = np.random.RandomState(seed)
+    inp = decode_random(seed, B=1, H=H, W=W, J=J)
+    hm = sigmoid(r.randn(1, cat, H, W))
+    if seam:
+        for c in range(cat - 1):
+            hm[0, c + 1, 0, 4:7] = np.array([3.0, 3.25, 3.5]) + c / 16.0       # "below" the peak (H-1, 5) of plane c
+            hm[0, c, H - 1, W - 7:W - 4] = np.array([4.0, 4.25, 4.5]) + c / 16.0   # "above" the peak (0, W-6) of plane c + 1
+        for (c, y, x, v) in seam_peaks(cat, H, W):
+            hm[0, c, y, x] = v
+    inp["hm"] = hm
+    return inp
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Zeros inside the top-K, quantised ties, signed maps (the oracle's order rule is the reference: value desc, flat index asc)
+def decode_sparse(seed, H, W, J=2):
+    """Every plane: 20..60 planted, distinct positive values, zeros everywhere else."""
+    r = np.random.RandomState(seed)
+    inp = decode_random(seed, B=1, H=H, W=W, J=J)
+    for key in ("hm", "hm_hp"):
+        m = np.zeros_like(inp[key])
+        for plane in m.reshape(-1, H * W):
+            n = r.randint(20, 61)
+            plane[r.choice(H * W, n, replace=False)] = ((r.permutation(4096)[:n] + 1) / 4096.0).astype(F32)
+        inp[key] = m
+    return inp
+
+
+def decode_quantised(seed, H, W, J=2):
+    inp = decode_random(seed, B=1, H=H, W=W, J=J)
+    for key in ("hm", "hm_hp"):
+        inp[key] = (np.round(inp[key] * 16) / 16).astype(F32)
+    return inp
+
+
+def decode_signed(seed, H, W, J=2, zeros=0):
+    """hm / hm_hp straight from randn (no sigmoid).  zeros > 0: that many true zeros planted per plane, and two 5 x 5 patches made
+    negative throughout (below -1, their centres -0.25 and -0.5), so that the plane has negative PEAKS (the maximum of nine normal
+    values is hardly ever negative)."""
+    r = np.random.RandomState(seed)
+    inp = decode_random(seed, B=1, H=H, W=W, J=J)
+    for key in ("hm", "hm_hp"):
+        m = r.randn(*inp[key].shape).astype(F32)
+        for plane in m.reshape(-1, H, W):
+            if zeros:
+                plane.reshape(-1)[r.choice(H * W, zeros, replace=False)] = 0.0
+                for y0, peak in ((1, -0.25), (H - 6, -0.5)):
+                    plane[y0:y0 + 5, y0:y0 + 5] = -np.abs(plane[y0:y0 + 5, y0:y0 + 5]) - F32(1)
+                    plane[y0 + 2, y0 + 2] = peak
+        inp[key] = m
+    return inp
+
+
+# name -> (seed, H, W, K): K small enough that only positive peaks are selected (asserted from the oracle where it is used)
+DECODE_SIGNED_CASES = {"signed_16x16": (601, 16, 16, 5), "signed_60x70": (602, 60, 70, 40), "signed_128x129": (603, 128, 129, 100)}

@@ -2,7 +2,7 @@
 (/root/reference, build container only).  The reference never travels: only the resulting
 .npz data files (inputs are regenerated from seeds by tests/cases.py) are committed.
 
-    python tests/golden/make_golden.py [decode] [nets] [dcn] [checks] [spec]
+    python tests/golden/make_golden.py [decode] [nets] [dcn] [checks] [spec] [decode_edges]
 """
 import os
 import sys
@@ -38,6 +38,62 @@ def gen_decode():
                             inds=inds[:, :K].numpy().astype(np.int32),
                             hm_inds=hinds[:, :, :K].numpy().astype(np.int32), tie_free=tie_free)
         print("decode", name, dets.shape, "tie_free", tie_free)
+
+
+def _ref_decode(inp, K, use_reg=True, use_off=True):
+    """The reference's multi_pose_decode with its own top-(K+1) peaks -> (dets, inds, clses, hm_inds, tie_free)."""
+    from models.decode import multi_pose_decode, _nms, _topk, _topk_channel
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    with torch.no_grad():
+        dets = multi_pose_decode(t["hm"], t["wh"], t["hps"], reg=t["reg"] if use_reg else None,
+                                 hm_hp=t["hm_hp"], hp_offset=t["hp_offset"] if use_off else None, K=K)
+        sc, inds, clses, _, _ = _topk(_nms(t["hm"]), K=K + 1)
+        hsc, hinds, _, _ = _topk_channel(_nms(t["hm_hp"]), K=K + 1)
+    tie_free = bool((np.diff(sc.numpy().astype(np.float64), axis=-1) < 0).all() and
+                    (np.diff(hsc.numpy().astype(np.float64), axis=-1) < 0).all())
+    return (dets.numpy(), inds[:, :K].numpy().astype(np.int32), clses[:, :K].numpy().astype(np.int32),
+            hinds[:, :, :K].numpy().astype(np.int32), tie_free)
+
+
+def distance_ties_are_harmless(cmp):
+    """True unless some (image, joint, centre) has its minimum distance at two candidates that differ in position or score --
+    the one case in which the reference's `min` over candidates (decode.py:289) could return either of two different answers."""
+    tied = cmp["dist"] == cmp["min_dist"][..., None]                                    # [B,J,K,M]
+    for key in ("cand_x", "cand_y", "cand_s"):
+        v = np.broadcast_to(cmp[key][:, :, None, :], tied.shape)
+        first = np.take_along_axis(v, cmp["min_ind"][..., None], axis=3)
+        if (tied & (v != first)).any():
+            return False
+    return True
+
+
+def gen_decode_edges():
+    """decode_edges.npz: the reference's outputs on the decision cases of tests/cases.py (outputs and flags only).
+    <case>__specified: the reference's result does not depend on an order torch leaves open (no tie inside the top-(K+1) of any
+    plane, no minimum distance shared by different candidates); where it is false the oracle's documented rule is the reference
+    (value descending then index ascending, first minimum).  <case>__agrees: the oracle equalled this torch build's output."""
+    from oracle import decode_np
+    data = {}
+
+    def record(name, inp, K, use_reg=True, use_off=True, clses=False):
+        dets, inds, cl, hm_inds, tie_free = _ref_decode(inp, K, use_reg, use_off)
+        od, aux = decode_np.multi_pose_decode(inp["hm"], inp["wh"], inp["hps"], inp["reg"] if use_reg else None, inp["hm_hp"],
+                                              inp["hp_offset"] if use_off else None, K=K, return_aux=True)
+        spec = bool(tie_free and distance_ties_are_harmless(aux["cmp"]))
+        agrees = bool(np.array_equal(od, dets) and np.array_equal(aux["inds"], inds) and np.array_equal(aux["hm_inds"], hm_inds))
+        data[name + "__dets"], data[name + "__inds"], data[name + "__hm_inds"] = dets, inds, hm_inds
+        if clses:
+            data[name + "__clses"] = cl
+        data[name + "__specified"], data[name + "__agrees"] = np.bool_(spec), np.bool_(agrees)
+        print("decode_edges", name, dets.shape, "specified", spec, "oracle agrees", agrees)
+
+    for name, c in cases.decode_assign_edges().items():
+        record(name, c["inp"], c["K"], c["use_reg"], c["use_off"])
+    for name, (cat, H, W, K, J, seed, seam) in cases.DECODE_MULTICAT_CASES.items():
+        record(name, cases.decode_multicat(cat, H, W, J, seed, seam), K, clses=True)
+    for name, (seed, H, W, K) in cases.DECODE_SIGNED_CASES.items():
+        record(name, cases.decode_signed(seed, H, W), K)
+    np.savez_compressed(os.path.join(HERE, "decode_edges.npz"), **data)
 
 
 def gen_flip():
@@ -92,6 +148,8 @@ if __name__ == "__main__":
     what = sys.argv[1:] or ["decode", "flip", "dcn", "nets"]
     if "decode" in what:
         gen_decode()
+    if "decode_edges" in what:
+        gen_decode_edges()
     if "flip" in what:
         gen_flip()
     if "checks" in what:
