@@ -218,6 +218,98 @@ def yuv_frame_geometry(shapes, strides, color="nv12", dtypes=None):
     return H, W, strides[0][0], strides[0][1], u_off, v_off, c_row, c_pix
 
 
+def frame_writable(shape, strides):
+    """Whether a view of the given shape and strides (in elements == bytes) may be WRITTEN: no two of its indices address the same
+    byte.  The dimensions with more than one index, sorted by stride: each stride must be at least the extent (last addressed offset
+    + 1) of the dimensions below it.  Sufficient, not necessary: crops, padded rows, planar and permuted views pass; expanded (stride
+    0) and overlapping (as_strided windows) views and negative strides do not.  A pure function of its arguments."""
+    dims = sorted((int(st), int(n)) for n, st in zip(shape, strides) if int(n) > 1)
+    if any(int(n) <= 0 for n in shape):
+        return False
+    extent = 1
+    for st, n in dims:
+        if st < extent:
+            return False
+        extent += (n - 1) * st
+    return True
+
+
+def byte_range(address, shape, strides):
+    """[first, last + 1) of the bytes a uint8 view with non-negative strides addresses from `address`."""
+    return int(address), int(address) + sum((int(n) - 1) * int(st) for n, st in zip(shape, strides)) + 1
+
+
+# cp_draw_style (include/centerpose_hip.h)
+DRAW_STYLE = np.dtype([("box_thickness", "<i4"), ("limb_radius", "<i4"), ("joint_radius", "<i4"), ("palette", "u1", (36, 4))])
+
+# the limbs of a pose in paint order, as joint pairs (COCO keypoint order: 0 nose, odd = left, even = right)
+DRAW_LIMBS = ((0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6), (5, 6), (5, 7), (7, 9), (6, 8), (8, 10), (5, 11), (6, 12), (11, 12), (11, 13),
+              (13, 15), (12, 14), (14, 16))
+# this project's palette, (B, G, R): one colour for left-side parts, one for right-side parts, one for mid-line parts and the box
+DRAW_LEFT, DRAW_RIGHT, DRAW_MID = (0, 140, 255), (255, 160, 0), (60, 220, 60)
+
+
+def _side_color(joints):
+    sides = {j % 2 for j in joints if j > 0}                   # the nose is on the mid-line
+    return DRAW_MID if len(sides) != 1 else (DRAW_LEFT if sides == {1} else DRAW_RIGHT)
+
+
+class DrawStyle:
+    """How draw_results paints: box_thickness 0..64 (0: no box), limb_radius -1 (no limbs) or 1..64, joint_radius -1 (no joints) or
+    0..64, and the colours as (B, G, R): one for the box, one per limb (DRAW_LIMBS order), one per joint.  Defaults: thickness 2, limb
+    radius 1, joint radius 2; a limb or joint on the left side DRAW_LEFT, on the right side DRAW_RIGHT, the box, the nose and the limbs
+    that join the two sides DRAW_MID."""
+
+    def __init__(self, box_thickness=2, limb_radius=1, joint_radius=2, box_color=None, limb_colors=None, joint_colors=None):
+        self.box_thickness, self.limb_radius, self.joint_radius = int(box_thickness), int(limb_radius), int(joint_radius)
+        self.box_color = tuple(box_color) if box_color is not None else DRAW_MID
+        self.limb_colors = [tuple(c) for c in limb_colors] if limb_colors is not None else [_side_color(ab) for ab in DRAW_LIMBS]
+        self.joint_colors = [tuple(c) for c in joint_colors] if joint_colors is not None else [_side_color((j,)) for j in range(17)]
+        if not (0 <= self.box_thickness <= 64):
+            raise _lib.CenterposeHipError("box_thickness %d outside 0..64" % self.box_thickness)
+        if not (self.limb_radius == -1 or 1 <= self.limb_radius <= 64):
+            raise _lib.CenterposeHipError("limb_radius %d is neither -1 nor in 1..64 (radius 0 would dot the lines)" % self.limb_radius)
+        if not (-1 <= self.joint_radius <= 64):
+            raise _lib.CenterposeHipError("joint_radius %d outside -1..64" % self.joint_radius)
+        if len(self.limb_colors) != 18 or len(self.joint_colors) != 17:
+            raise _lib.CenterposeHipError("a style has 18 limb colours and 17 joint colours")
+        for c in self.palette():
+            if len(c) != 3 or any(not (0 <= int(v) <= 255) for v in c):
+                raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
+
+    def palette(self):
+        """The 36 (B, G, R) colours in paint order: the box, the limbs, the joints."""
+        return [self.box_color] + list(self.limb_colors) + list(self.joint_colors)
+
+    def struct(self, matrix=None):
+        """One DRAW_STYLE record; `matrix` ("bt601" / "bt709"): the palette as (Y, U, V) for YUV frames."""
+        rec = np.zeros(1, DRAW_STYLE)
+        rec["box_thickness"], rec["limb_radius"], rec["joint_radius"] = self.box_thickness, self.limb_radius, self.joint_radius
+        pal = self.palette() if matrix is None else palette_to_yuv(self.palette(), matrix)
+        rec["palette"][0, :, :3] = np.asarray(pal, np.uint8)
+        return rec
+
+
+# limited-range BGR -> (Y, U, V) rows of (R, G, B) weights, 8 fractional bits
+YUV_FORWARD = {"bt601": ((66, 129, 25), (-38, -74, 112), (112, -94, -18)),
+               "bt709": ((47, 157, 16), (-26, -87, 112), (112, -102, -10))}
+
+
+def palette_to_yuv(colors, matrix="bt601"):
+    """(B, G, R) colours -> (Y, U, V) by the usual limited-range 8-bit forms, e.g. bt601 Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16,
+    U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128, V = ((112 R - 94 G - 18 B + 128) >> 8) + 128 (arithmetic shifts).  This is NOT
+    the inverse of csrc/yuv_arith.h's YUV -> BGR: a painted colour read back through the pre-process differs by a few levels."""
+    if matrix not in YUV_FORWARD:
+        raise _lib.CenterposeHipError("unknown matrix %r: one of %s" % (matrix, ", ".join(sorted(YUV_FORWARD))))
+    ky, ku, kv = YUV_FORWARD[matrix]
+    out = []
+    for b, g, r in colors:
+        b, g, r = int(b), int(g), int(r)
+        out.append((((ky[0] * r + ky[1] * g + ky[2] * b + 128) >> 8) + 16, ((ku[0] * r + ku[1] * g + ku[2] * b + 128) >> 8) + 128,
+                    ((kv[0] * r + kv[1] * g + kv[2] * b + 128) >> 8) + 128))
+    return out
+
+
 class _Staging:
     """A pinned host buffer that grows on demand, and ONE stream-ordered upload of its first bytes per use.  `host()` waits for the
     previous upload to have left the buffer before handing it out again (an event on that copy alone, not a device synchronisation)."""
@@ -621,7 +713,7 @@ class BaseDetector(object):
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601"):
+    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -636,9 +728,18 @@ class BaseDetector(object):
         `matrix`): a list of plane tuples or surface tensors as for pre_process_batch, the rules per plane; the results equal those of
         the converted BGR host arrays.
         return_device=True (host or device input): the rows as ONE device tensor float32 [N, S*K, 56] in input order instead of the
-        list -- no download and no synchronisation; the tensor is ready in the current stream's order."""
+        list -- no download and no synchronisation; the tensor is ready in the current stream's order.
+        draw=True (device frames only): once the rows are in input order the frames are painted with them, in place, as
+        draw_results(images, rows, layout, color, matrix) does with the default threshold and style -- whose rules for writable frames
+        apply and are checked before anything is launched.  The return value is exactly what it is without `draw`."""
+        given = images
         images, frames = self._batch_input(images, layout, color, matrix)
         coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+        if draw:
+            if frames is None and images:
+                raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
+                                              "there is no CPU fallback")
+            self._check_writable(given, images, color)
         if not images:
             return torch.empty((0, 0, 56), dtype=torch.float32, device="cuda") if return_device else []
         shapes = [im.shape[0:2] for im in images] if frames is None else [f[1:3] for f in frames]
@@ -651,7 +752,7 @@ class BaseDetector(object):
                 work.append((table, scratch_bytes, inp_h, inp_w))
                 parts += [table, self._inverse_affines(metas)]
         order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
-        if return_device and len(groups) > 1:
+        if (return_device or draw) and len(groups) > 1:
             parts.append(np.argsort(np.asarray(order, np.int64)).astype(np.int64))       # rides in the one table upload
         staging = self._upload_images(images, offsets, nbytes) if frames is None else None
         parts = self._upload_table(parts)
@@ -669,6 +770,11 @@ class BaseDetector(object):
                 per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
             merged.append(self.merge_outputs_batch(per_scale))
         rows = merged[0] if len(merged) == 1 else torch.cat(merged, 0)
+        if draw:
+            ordered = rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
+            self._draw(images, frames, ordered, color, matrix, None, None)
+            if return_device:
+                return ordered
         if return_device:
             return rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
         rows = rows.cpu().numpy()                                                               # the one download
@@ -676,6 +782,103 @@ class BaseDetector(object):
         for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
         return results
+
+    @staticmethod
+    def _check_writable(given, images, color):
+        """Raise unless every frame of a call may be written: every tensor a view without self-overlap (frame_writable), the luma
+        bytes of a plane tuple apart from its chroma bytes, and no tensor given twice."""
+        if isinstance(given, torch.Tensor) and not frame_writable(given.shape, given.stride()):
+            raise _lib.CenterposeHipError("the frames tensor of shape %s and strides %s cannot be written: two of its indices address the "
+                                          "same byte" % (tuple(given.shape), tuple(given.stride())))
+        seen = set()
+        for n, im in enumerate(images):
+            planes = [im] if isinstance(im, torch.Tensor) else list(im)
+            for t in planes:
+                if not frame_writable(t.shape, t.stride()):
+                    raise _lib.CenterposeHipError("frame %d: a view of shape %s and strides %s cannot be written: two of its indices address "
+                                                  "the same byte (expanded or overlapping view)" % (n, tuple(t.shape), tuple(t.stride())))
+                key = (t.data_ptr(), tuple(t.shape), tuple(t.stride()))
+                if key in seen:
+                    raise _lib.CenterposeHipError("frame %d: the same tensor is given twice in one call" % n)
+                seen.add(key)
+            if color in YUV_COLORS and len(planes) > 1:
+                y0, y1 = byte_range(planes[0].data_ptr(), planes[0].shape, planes[0].stride())
+                for t in planes[1:]:
+                    c0, c1 = byte_range(t.data_ptr(), t.shape, t.stride())
+                    if c0 < y1 and y0 < c1:
+                        raise _lib.CenterposeHipError("frame %d: the luma plane and a chroma plane share bytes" % n)
+
+    def _draw(self, images, frames, rows, color, matrix, vis_thresh, style):
+        """cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8 for checked frames (`_frame` / `_yuv_frame` per image) and device rows
+        [N,M,56]: one table upload, two launches in the current stream."""
+        yuv = color in YUV_COLORS
+        style = DrawStyle() if style is None else style
+        if not isinstance(style, DrawStyle):
+            raise _lib.CenterposeHipError("style is a DrawStyle (got %s)" % type(style).__name__)
+        vis_thresh = float(self.cfg.TEST.VIS_THRESH if vis_thresh is None else vis_thresh)
+        N, M = len(images), int(rows.shape[1])
+        if N == 0 or M == 0:
+            return
+        table = np.zeros(N, YUV_FRAME_DESC if yuv else FRAME_DESC)
+        for n, f in enumerate(frames):
+            d = table[n]
+            if yuv:
+                d["y_base"], d["H"], d["W"], d["y_row"], d["y_pix"], d["u_base"], d["v_base"], d["c_row"], d["c_pix"] = f
+            else:
+                d["base"], d["H"], d["W"], d["row_stride"], d["pix_stride"], d["ch_off"] = f
+            d["NH"], d["NW"], d["mid_off"] = d["H"], d["W"], -1
+        table = np.ascontiguousarray(table)
+        rec = style.struct(matrix if yuv else None)
+        L = _lib.lib()
+        L.cp_draw_scratch_bytes.restype = ctypes.c_size_t
+        nbytes = int(L.cp_draw_scratch_bytes(N, M))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=rows.device)
+        table_dev, = self._upload_table([table])
+        fn = L.cp_draw_rows_yuv_frames_u8 if yuv else L.cp_draw_rows_frames_u8
+        rc = fn(ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), N, ctypes.c_void_p(rows.data_ptr()), M,
+                ctypes.c_float(vis_thresh), rec.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(scratch.data_ptr()),
+                ctypes.c_size_t(nbytes), _lib.stream())
+        _lib.check(rc, "cp_draw_rows_yuv_frames_u8" if yuv else "cp_draw_rows_frames_u8")
+
+    def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None):
+        """Paint the detections `rows` onto `frames`, in place, on the device, in the current stream -> `frames`.  What is drawn is
+        what the reference's show_results draws, without the text: per row with score > vis_thresh (default cfg.TEST.VIS_THRESH) the
+        box, the limbs whose two joints both score > 0 and the joints that score > 0, opaque, rows in ascending order, box then limbs
+        then joints, the last painted wins.  The rule is this project's own, integer-only and bit-exact between the device, the host
+        painter cp_draw_rows_frames_host and a NumPy restatement (csrc/draw_arith.h).
+        frames: as for pre_process_batch -- a list of CUDA uint8 tensors or one 4-D tensor (`layout`, `color`, C = 3 or 4), or with
+        color "nv12" / "nv21" / "i420" a list of plane tuples / surface tensors; for those the palette is converted to (Y, U, V) with
+        `matrix` (palette_to_yuv), luma is written per pixel and a chroma sample takes the latest-painted colour among its 2x2 pixels.
+        Three bytes per covered pixel: a fourth channel, row padding and everything outside a view keep their bytes.
+        rows: CUDA float32 [N, M, 56] in image coordinates, as run_batch(..., return_device=True) returns them ([M, 56]: one frame).
+        style: a DrawStyle.  The descriptor table is the only upload; nothing is downloaded and nothing synchronises.
+        A frame is WRITTEN here, so beyond the stream-order and lifetime rules of pre_process_batch, which hold unchanged: every tensor
+        must be a view in which no two indices address one byte (frame_writable: expanded and overlapping views raise), a plane
+        tuple's luma bytes must lie apart from its chroma bytes, the same tensor may not be given twice -- and that the frames of one
+        call share no bytes otherwise is the caller's promise.  Host arrays raise: there is no CPU fallback."""
+        given = frames
+        images, descs = self._batch_input(frames, layout, color, matrix)
+        if descs is None and images:
+            raise _lib.CenterposeHipError("draw_results paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
+                                          "there is no CPU fallback")
+        if isinstance(rows, np.ndarray) or not isinstance(rows, torch.Tensor):
+            raise _lib.CenterposeHipError("rows must be a CUDA float32 tensor [N, M, 56] on the device (got %s): there is no CPU fallback"
+                                          % type(rows).__name__)
+        if rows.dim() == 2:
+            rows = rows.unsqueeze(0)
+        if rows.dim() != 3 or rows.shape[2] != 56:
+            raise _lib.CenterposeHipError("rows must be [N, M, 56] (or [M, 56] for one frame), got shape %s" % (tuple(rows.shape),))
+        if not rows.is_cuda:
+            raise _lib.CenterposeHipError("rows on %s: they must be on the model's GPU; there is no CPU fallback" % rows.device)
+        if rows.device != self._model_device():
+            raise _lib.CenterposeHipError("rows on %s, the model is on %s" % (rows.device, self._model_device()))
+        if rows.dtype != torch.float32:
+            raise _lib.CenterposeHipError("rows must be float32 (got %s)" % rows.dtype)
+        if rows.shape[0] != len(images):
+            raise _lib.CenterposeHipError("rows hold %d blocks for %d frames" % (rows.shape[0], len(images)))
+        self._check_writable(given, images, color)
+        self._draw(images, descs or [], rows.detach().contiguous(), color, matrix, vis_thresh, style)
+        return given
 
     def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):
         if isinstance(x, (np.ndarray, torch.Tensor)) or (color in YUV_COLORS and isinstance(x, (tuple, list))):

@@ -437,6 +437,52 @@ int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* table_host, i
 int cp_yuv_to_bgr_host(const unsigned char* y, const unsigned char* u, const unsigned char* v, size_t n, const int* coef,
                        unsigned char* bgr);
 
+/* ---- draw the detections onto device frames, in place (draw_results / run_batch(draw=True)) ------------------------------------------
+ * The box, the 18 limbs and the 17 joints of every row of rows[N,M,56] (box 0:4, score 4, joints 5:39, joint scores 39:56, image
+ * coordinates) whose score is > vis_thresh, painted onto frame n = 0..N-1 with its own M rows.  Opaque: a frame is never read; bytes
+ * that no primitive covers -- a fourth channel, row padding, everything outside H x W -- are not written.  The picture is this library's
+ * own rule (csrc/draw_arith.h), integer-only after the first step:
+ *   coordinates: a non-finite one (by the float's bits) kills its primitive; any other is clamped to [-16384, 16383] and truncated
+ *     toward zero.  Primitives of a row in paint order, the index being the palette entry: 0 the box (exists iff its four coordinates
+ *     are alive), 1..18 the limbs (0,1) (0,2) (1,3) (2,4) (3,5) (4,6) (5,6) (5,7) (7,9) (6,8) (8,10) (5,11) (6,12) (11,12) (11,13) (13,15)
+ *     (12,14) (14,16) (both joint scores > 0, four coordinates alive), 19..35 the joints (score > 0, both coordinates alive).
+ *   coverage of pixel p, k = R * R + R: joint at P: |p - P|^2 <= k.  Limb P -> Q: a = p - P, d = Q - P, L2 = d.d, t = a.d; L2 = 0 or
+ *     t <= 0: a.a <= k; t >= L2: |p - Q|^2 <= k; otherwise (a x d)^2 <= k * L2.  Box of thickness T, corners sorted: inside the closed
+ *     rectangle and x - x0 < T or x1 - x < T or y - y0 < T or y1 - y < T.
+ *   order: rows ascending, primitives in paint order, the last one that covers a pixel gives its colour.
+ * cp_draw_style: box_thickness 0..64 (0: no box), limb_radius -1 (no limbs) or 1..64, joint_radius -1 (no joints) or 0..64; palette[l]
+ *   bytes 0..2: what primitive l stores -- for cp_frame_desc frames byte k goes to ch_off[k] (k = 0, 1, 2: B, G, R of a BGR or RGB
+ *   frame described as for the pre-process), for cp_yuv_frame_desc frames they are (Y, U, V).  Byte 3 is not used.
+ * cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8: two launches on `stream` (draw_build_kernel: one wave per row builds the
+ *   primitive records and the row's bounding box into scratch; draw_raster_kernel: one block per 16x16 pixel tile -- 32x32 for YUV,
+ *   where a thread owns a 2x2 block -- and frame finds every pixel's last covering primitive and stores it).  table: DEVICE
+ *   cp_frame_desc[N] / cp_yuv_frame_desc[N], table_host: the same descriptors on the HOST; only the addressing fields and H, W are
+ *   read.  rows: DEVICE float32 [N,M,56].  style: HOST.  scratch: DEVICE, 16-byte aligned, at least cp_draw_scratch_bytes(N, M) bytes,
+ *   contents undefined before and after.  YUV frames: luma per covered pixel; chroma sample (i, j) is written iff one of the luma
+ *   pixels (2i..2i+1, 2j..2j+1) inside the frame is covered and takes the colour of the latest-painted winner among them.
+ *   Checked before anything is launched (rc 1, cp_last_error): null pointers, 0 <= N <= 65535, 0 <= M <= 2^24 and N * M <= 2^28, a
+ *   finite vis_thresh, the style ranges, the scratch size and alignment, and per frame: bases non-null, H and W in 1..16384, no negative
+ *   stride or offset, a positive stride along every dimension with more than one index, distinct ch_off / distinct U and V bases,
+ *   addressed offsets below 2^62.  N = 0 or M = 0 succeeds and launches nothing.  The caller vouches for the frames' memory, stream
+ *   order and lifetime as for the pre-process, and ALSO that no two addressed bytes of one call coincide (within a frame or between
+ *   frames): a frame is written here.  cp_last_kernel(): draw_raster_kernel<bgr|yuv>.
+ * cp_draw_rows_frames_host / cp_draw_rows_yuv_frames_host: HOST only -- sequential painters over the same descriptors holding host
+ *   addresses and host rows, built from the same statements; same checks.  What the device result is pinned to, byte for byte. */
+typedef struct cp_draw_style {      /* 156 bytes */
+    int box_thickness;
+    int limb_radius;
+    int joint_radius;
+    unsigned char palette[36][4];
+} cp_draw_style;
+int cp_sizeof_draw_style(void);
+size_t cp_draw_scratch_bytes(int N, int M);
+int cp_draw_rows_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                           const void* style, void* scratch, size_t scratch_bytes, void* stream);
+int cp_draw_rows_yuv_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                               const void* style, void* scratch, size_t scratch_bytes, void* stream);
+int cp_draw_rows_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
+int cp_draw_rows_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
