@@ -62,6 +62,9 @@ extern "C" int cp_maxpool2d_nhwc_f32(const float* in, int inLd, float* out, int 
                                      int s, int p, void* stream)
 {
     CP_CHECK_ARG(in && out && C % 4 == 0 && inLd % 4 == 0 && outLd % 4 == 0, "maxpool: C, ld must be multiples of 4");
+    CP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0, "maxpool: B=%d H=%d W=%d C=%d must be positive", B, H, W, C);
+    CP_CHECK_ARG(k >= 1 && s >= 1 && p >= 0 && p < k, "maxpool: k=%d s=%d p=%d (k >= 1, s >= 1, 0 <= p < k)", k, s, p);
+    CP_CHECK_ARG(H + 2 * p >= k && W + 2 * p >= k, "maxpool: Ho, Wo: window k=%d p=%d larger than the %d x %d map", k, p, H, W);
     const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
     CP_CHECK_ARG((long long)Wo * (C / 4) * (C / 4) < (1ll << 32) && (long long)B * Ho < (1ll << 31), "maxpool: row too large");
     const EwRow r = ew_row(B * Ho, Wo, C / 4);
@@ -179,6 +182,7 @@ extern "C" int cp_dw_deconv_add_nhwc_f32(const float* in, int inLd, const float*
     CP_CHECK_ARG(in && w && out && C % 4 == 0 && inLd % 4 == 0 && outLd % 4 == 0 && (!add || addLd % 4 == 0),
                  "dw_deconv_add: C, ld must be multiples of 4");
     CP_CHECK_ARG(f >= 1, "dw_deconv_add: f=%d", f);
+    CP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0, "dw_deconv_add: B=%d H=%d W=%d C=%d must be positive", B, H, W, C);
     CP_CHECK_ARG((long long)W * f * (C / 4) * (C / 4) < (1ll << 32) && (long long)B * H * f < (1ll << 31), "dw_deconv_add: row too large");
     // CP_DWDECONV2=0: the generic kernel for f = 2 as well (A/B switch: tests compare the two bit for bit; read per call -- launches
     // are recorded once per plan, not per step)
@@ -259,6 +263,12 @@ extern "C" int cp_sum_up_nhwc_f32(int n, const float* const* src, const int* ld,
                                   int B, int H, int W, int C, int relu, void* stream)
 {
     CP_CHECK_ARG(n >= 1 && n <= 4 && src && ld && shift && out && C % 4 == 0, "sum_up: bad arguments");
+    CP_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0, "sum_up: B=%d H=%d W=%d C=%d must be positive", B, H, W, C);
+    // source j has (H >> shift) x (W >> shift) pixels and the kernel reads its row y >> shift: an H or W the up-sampling factor does not
+    // divide would index one row / column past the source (checked here, not in the kernel)
+    for (int i = 0; i < n; ++i)
+        CP_CHECK_ARG(shift[i] >= 0 && shift[i] < 31 && H % (1 << shift[i]) == 0 && W % (1 << shift[i]) == 0,
+                     "sum_up: source %d: shift=%d must be >= 0 and 2^shift must divide H=%d and W=%d", i, shift[i], H, W);
     SumUpArgs a;
     for (int i = 0; i < 4; ++i) { a.src[i] = i < n ? src[i] : nullptr; a.ld[i] = i < n ? ld[i] : 0; a.sh[i] = i < n ? shift[i] : 0; }
     a.n = n;
@@ -313,6 +323,10 @@ extern "C" int cp_sum_up_group_nhwc_f32(int n, const float* const* src, const in
         const int ns = mt[0], B = mt[10], H = mt[11], W = mt[12], C = mt[13];
         if (k < n) {
             CP_CHECK_ARG(ns >= 1 && ns <= 4 && out[k] && C > 0 && C % 4 == 0 && mt[9] % 4 == 0, "sum_up_group: member %d: bad arguments", k);
+            CP_CHECK_ARG(B > 0 && H > 0 && W > 0, "sum_up_group: member %d: B=%d H=%d W=%d must be positive", k, B, H, W);
+            for (int i = 0; i < ns; ++i)
+                CP_CHECK_ARG(mt[5 + i] >= 0 && mt[5 + i] < 31 && H % (1 << mt[5 + i]) == 0 && W % (1 << mt[5 + i]) == 0,
+                             "sum_up_group: member %d source %d: shift=%d must be >= 0 and 2^shift must divide H=%d and W=%d", k, i, mt[5 + i], H, W);
             CP_CHECK_ARG((long long)W * (C / 4) * (C / 4) < (1ll << 32) && (long long)B * H < (1ll << 31), "sum_up_group: member %d: row too large", k);
         }
         for (int i = 0; i < 4; ++i) {
@@ -370,6 +384,10 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ in, int inLd, int 
 extern "C" int cp_nchw_to_nhwc_f32(const float* in, float* out, int B, int C, int H, int W, int outLd, int cOff, void* stream)
 {
     CP_CHECK_ARG(in && out && outLd >= cOff + C, "nchw_to_nhwc: bad arguments");
+    CP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && cOff >= 0, "nchw_to_nhwc: B=%d C=%d H=%d W=%d must be positive, cOff=%d >= 0", B, C, H, W, cOff);
+    CP_CHECK_ARG(B <= 65535, "nchw_to_nhwc: B=%d exceeds the grid limit 65535", B);
+    CP_CHECK_ARG(cp_cdiv(C, 32) <= 65535, "nchw_to_nhwc: C=%d exceeds the grid limit of 65535 blocks of 32 channels", C);
+    CP_CHECK_ARG((long long)H * W < (1ll << 31), "nchw_to_nhwc: H=%d x W=%d exceeds 2^31 pixels", H, W);
     const int HW = H * W;
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cp_cdiv(HW, 32), cp_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, in, out,
                        C, HW, outLd, cOff);
@@ -379,6 +397,10 @@ extern "C" int cp_nchw_to_nhwc_f32(const float* in, float* out, int B, int C, in
 extern "C" int cp_nhwc_to_nchw_f32(const float* in, int inLd, int cOff, float* out, int B, int C, int H, int W, void* stream)
 {
     CP_CHECK_ARG(in && out && inLd >= cOff + C, "nhwc_to_nchw: bad arguments");
+    CP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && cOff >= 0, "nhwc_to_nchw: B=%d C=%d H=%d W=%d must be positive, cOff=%d >= 0", B, C, H, W, cOff);
+    CP_CHECK_ARG(B <= 65535, "nhwc_to_nchw: B=%d exceeds the grid limit 65535", B);
+    CP_CHECK_ARG(cp_cdiv(C, 32) <= 65535, "nhwc_to_nchw: C=%d exceeds the grid limit of 65535 blocks of 32 channels", C);
+    CP_CHECK_ARG((long long)H * W < (1ll << 31), "nhwc_to_nchw: H=%d x W=%d exceeds 2^31 pixels", H, W);
     const int HW = H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(cp_cdiv(HW, 32), cp_cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, in, inLd,
                        cOff, out, C, HW);
@@ -535,6 +557,7 @@ __global__ void global_avgpool_kernel(const float* __restrict__ in, int inLd, fl
 extern "C" int cp_global_avgpool_nhwc_f32(const float* in, int inLd, float* out, int outLd, int B, int HW, int C, void* stream)
 {
     CP_CHECK_ARG(in && out && C % 4 == 0 && inLd % 4 == 0 && outLd % 4 == 0 && B > 0 && HW > 0 && B <= 65535, "global_avgpool: bad arguments");
+    CP_CHECK_ARG(C > 0 && inLd >= C && outLd >= C, "global_avgpool: inLd=%d and outLd=%d must be >= C=%d > 0", inLd, outLd, C);
     hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)cp_cdiv(C / 4, 32), (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, inLd,
                        out, outLd, HW, C / 4);
     cp_note_kernel("global_avgpool_kernel");

@@ -629,9 +629,17 @@ def shuffle_concat(x1, x2, out, h, hp):
     return out
 
 
+def _check_up_shifts(shifts, H, W):
+    """a source up-sampled by 2^shift has (H >> shift) x (W >> shift) pixels: the factor must divide the output map, or the kernel would
+    read one row / column past the source (the launcher refuses the same)"""
+    assert all(s >= 0 and H % (1 << s) == 0 and W % (1 << s) == 0 for s in shifts), \
+        "sum_up: every 2^shift must divide the %d x %d output (shifts %s)" % (H, W, list(shifts))
+
+
 def sum_up_launch(srcs, shifts, out, relu):
     B, H, W, C = out.shape
     n = len(srcs)
+    _check_up_shifts(shifts, H, W)
     return Launch("cp_sum_up_nhwc_f32", None, list(srcs) + [None] * (4 - n) + [out],
                   [n] + [_ld(s) for s in srcs] + [0] * (4 - n) + list(shifts) + [0] * (4 - n) + [_ld(out), B, H, W, C, 1 if relu else 0])
 
@@ -646,6 +654,7 @@ def sum_up_group_launch(members, whole, relu):
         B, H, W, C = out.shape
         k = len(srcs)
         assert 1 <= k <= 4 and out.untyped_storage().data_ptr() == whole.untyped_storage().data_ptr()
+        _check_up_shifts(shifts, H, W)
         ptrs += list(srcs) + [None] * (4 - k)
         outs.append(out)
         meta += [k] + [_ld(t) for t in srcs] + [0] * (4 - k) + list(shifts) + [0] * (4 - k) + [_ld(out), B, H, W, C]

@@ -354,7 +354,12 @@ def evaluate(hook, sd, args, get, dt, wino=None, om=None):
         xv, sv = get(x, False), get(se, False)
         if add is None:
             return [Out((xv * sv).to(dt), exact=True)]
-        return [Out((xv * sv + get(add, False)).to(dt), exact=True)]   # two roundings: the library is built with contraction off
+        # two roundings.  Not because of a build flag: seven objects of csrc/Makefile are built with -ffp-contract=off, elementwise.o is
+        # not (it would change the bits of DLA-34's up-sampling).  scale_add_kernel forms the float4 product as one statement and adds
+        # the addend in a later, conditional one, and the compiler keeps them apart (a packed multiply, then a packed add); should a
+        # compiler ever fuse them, the two roundings are to be made explicit in that kernel, not loosened here.
+        # tests/test_helper_parity_hip.py holds the kernel to the same two roundings over multi-block rows and strided views.
+        return [Out((xv * sv + get(add, False)).to(dt), exact=True)]
     if hook == "emit_shuffle":
         x1, x2 = args
         c = torch.cat([g(x1), g(x2)], 1)

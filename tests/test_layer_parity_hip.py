@@ -24,7 +24,8 @@ ENVS = {"default": {}, "nogroup_nowino": {"CP_GROUP": "0", "CP_WINOGRAD": "0"}, 
 SHAPES = [(a, 2, 64, 96) for a in lo.ARCHS] + [("dla_34", 3, 160, 96)]
 CASES = [s + (e,) for s in SHAPES for e in ("default", "nogroup_nowino")] + [("dla_34", 3, 160, 96, "wino24"), ("res_50", 2, 64, 96, "wino24")]
 MUST_COVER = ("igemm_conv_kernel", "pw_conv_kernel", "conv3x3_patch_kernel", "conv3x3_c16_kernel", "conv3x3_wino_kernel", "conv3x3_wino24_kernel",
-              "conv3x3_wino24_group", "dcn_igemm_kernel", "stem7x7", "splitk_reduce_kernel", "dw_deconv2_add_kernel", "sum_up",
+              "conv3x3_wino24_group", "dcn_igemm_kernel", "stem7x7", "splitk_reduce_kernel", "dw_deconv2_add_kernel", "dw_deconv_add_kernel",
+              "maxpool_nhwc_kernel", "sum_up",
               "dwconv_nhwc_kernel", "global_avgpool_kernel", "scale_add_kernel", "shuffle_concat_kernel")
 _reports = {}
 
