@@ -404,7 +404,8 @@ static bool w24_fast_epilogue(const ConvArgs& a)
 {
     return (a.outLd & 3) == 0 && (a.Cout & 3) == 0 && (((size_t)a.out) & 15) == 0 &&
            (!a.res || ((a.resLd & 3) == 0 && (((size_t)a.res) & 15) == 0)) && (a.act == CP_ACT_NONE || a.act == CP_ACT_RELU) &&
-           (long long)a.W * a.outLd * 8 < (1ll << 31) && (long long)a.W * a.resLd * 8 < (1ll << 31);
+           // w24_output_all<true> forms (4 * it + aa) * ostep, up to 13 output rows, in `int`
+           (long long)a.W * a.outLd * 16 < (1ll << 31) && (long long)a.W * a.resLd * 16 < (1ll << 31);
 }
 
 static unsigned w24_magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }

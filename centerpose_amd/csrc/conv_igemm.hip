@@ -338,7 +338,15 @@ static int conv_args_from_desc(const cp_conv_desc* d, const float* const* src, c
     a.res = res; a.resLd = d->resLd; a.out = out; a.outLd = d->outLd; a.Cout = d->Cout;
     a.outNCHW = d->outNCHW; a.OH = d->OH; a.OW = d->OW; a.osy = d->osy; a.osx = d->osx; a.ooy = d->ooy; a.oox = d->oox;
     a.act = d->act; a.om = nullptr; a.omLd = 0; a.omMaskOff = 0; a.omSigmoid = 0; a.dg = 1; a.dily = a.dilx = 1; a.ksplit = d->ksplit > 1 ? d->ksplit : 1; a.nsub = d->nsub > 1 ? d->nsub : 1;
-    CP_CHECK_ARG(a.M > 0 && (long long)d->B * d->H * d->W < (1ll << 31), "conv2d: bad problem size");
+    CP_CHECK_ARG(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && (long long)d->B * d->H * d->W < (1ll << 31),
+                 "conv2d: bad problem size");
+    // M = B*Ho*Wo and the row index m0 + (up to 255) of the last block tile are `int`
+    CP_CHECK_ARG((long long)d->B * d->Ho * d->Wo + 255 < (1ll << 31), "conv2d: B*Ho*Wo=%lld output pixels exceed the 32-bit row index (limit %lld)",
+                 (long long)d->B * d->Ho * d->Wo, (1ll << 31) - 256);
+    // NCHW (stem) source: the producers form the image base b*C*H*W in `int` (igemm_conv_block, stem7x7.hip)
+    if (d->inNCHW)
+        CP_CHECK_ARG((long long)d->B * d->srcC[0] * d->H * d->W < (1ll << 31), "conv2d: NCHW source of B*C*H*W=%lld floats exceeds the 32-bit element index (limit %lld)",
+                     (long long)d->B * d->srcC[0] * d->H * d->W, (1ll << 31) - 1);
     for (int i = 0; i < d->nsrc && !d->inNCHW; ++i)
         CP_CHECK_ARG((long long)d->B * d->H * d->W * d->srcLd[i] * 4 < (1ll << 32), "conv2d: source %d exceeds 32-bit byte offsets", i);
     CP_CHECK_ARG(!(res && d->outNCHW), "conv2d: residual with NCHW output is not supported");

@@ -246,11 +246,14 @@ extern "C" int cp_head_points_f32(const float* feat, int featLd, const int* ws_i
                                   const float* b2, float* out, int B, int H, int W, int C, int J, int K, int hc, void* stream)
 {
     CP_CHECK_ARG(feat && ws_inds && w1 && b1 && w2 && b2 && out, "head_points: null pointer");
-    CP_CHECK_ARG(B > 0 && H > 0 && W > 0 && J > 0 && K > 0 && K <= 256 && K <= H * W, "head_points: bad shape");
+    CP_CHECK_ARG(B > 0 && H > 0 && W > 0 && J > 0 && K > 0 && K <= 256 && K <= (long long)H * W, "head_points: bad shape");
     CP_CHECK_ARG(C > 0 && C % 16 == 0 && C <= 512, "head_points: C=%d must be a multiple of 16 in 16..512 (physical channels)", C);
     CP_CHECK_ARG(featLd >= C && featLd % 4 == 0 && ((size_t)feat & 15) == 0, "head_points: feat must be 16-B aligned with ld %% 4 == 0 (ld %d)", featLd);
     CP_CHECK_ARG(hc > 0 && hc % 32 == 0 && hc <= 512, "head_points: head_conv=%d must be a multiple of 32 up to 512", hc);
     CP_CHECK_ARG((long long)B * (1 + J) * K < (1ll << 31) && (long long)B * H * W * (6 + 2 * J) < (1ll << 40), "head_points: too large");
+    // the kernel keeps H * W, a point's plane index and the pixel row b * H + y in `int`
+    CP_CHECK_ARG((long long)H * W < (1ll << 31) && (long long)B * H < (1ll << 31),
+                 "head_points: too large: H*W=%lld and B*H=%lld must stay below 2^31 (32-bit plane and row indices)", (long long)H * W, (long long)B * H);
     const int ns = (hc % 64 == 0 && hc >= 128) ? 2 : 1;
     const int nthr = 64 * hc / (32 * ns);
     const int nct = cp_cdiv(B * K, HP_M), njt = cp_cdiv(B * J * K, HP_M);
@@ -279,12 +282,13 @@ extern "C" int cp_head_points_pairs_f32(const float* feat, int featLd, const int
 {
     CP_CHECK_ARG(feat && ws_inds && w1 && b1 && w2 && b2 && out, "head_points_pairs: null pointer");
     CP_CHECK_ARG(perm, "head_points_pairs: the joint permutation is needed (device int[J])");
-    CP_CHECK_ARG(N > 0 && H > 0 && W > 0 && J > 0 && K > 0 && K <= 256 && K <= H * W, "head_points_pairs: bad shape");
+    CP_CHECK_ARG(N > 0 && H > 0 && W > 0 && J > 0 && K > 0 && K <= 256 && K <= (long long)H * W, "head_points_pairs: bad shape");
     CP_CHECK_ARG(C > 0 && C % 16 == 0 && C <= 512, "head_points_pairs: C=%d must be a multiple of 16 in 16..512 (physical channels)", C);
     CP_CHECK_ARG(featLd >= C && featLd % 4 == 0 && ((size_t)feat & 15) == 0, "head_points_pairs: feat must be 16-B aligned with ld %% 4 == 0 (ld %d)", featLd);
     CP_CHECK_ARG(hc > 0 && hc % 32 == 0 && hc <= 512, "head_points_pairs: head_conv=%d must be a multiple of 32 up to 512", hc);
     CP_CHECK_ARG((long long)N * (1 + J) * K < (1ll << 31) && (long long)2 * N * H * W * (6 + 2 * J) < (1ll << 40) && (long long)2 * N * H < (1ll << 31),
                  "head_points_pairs: too large");
+    CP_CHECK_ARG((long long)H * W < (1ll << 31), "head_points_pairs: too large: H*W=%lld must stay below 2^31 (32-bit plane index)", (long long)H * W);
     const int ns = (hc % 64 == 0 && hc >= 128) ? 2 : 1;
     const int nthr = 64 * hc / (32 * ns);
     const int nct = cp_cdiv(N * K, HP_M), njt = cp_cdiv(N * J * K, HP_M);

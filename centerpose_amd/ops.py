@@ -291,6 +291,7 @@ def conv2d_launch(srcs, wp, scale, shift, out, *, kh, kw, stride=1, pad=0, cout,
         x = srcs[0]
         B, C, H, W = x.shape
         d.srcC[0], d.srcLd[0] = C, 0
+        assert B * C * H * W < 2 ** 31, "conv2d: NCHW source of %d floats exceeds the 32-bit element index of the stem producers" % (B * C * H * W)
         assert x.is_contiguous()
     else:
         B, H, W, _ = srcs[0].shape
@@ -301,6 +302,7 @@ def conv2d_launch(srcs, wp, scale, shift, out, *, kh, kw, stride=1, pad=0, cout,
     if Ho is None:
         Ho = (H + 2 * py - kh) // stride + 1
         Wo = (W + 2 * px - kw) // stride + 1
+    assert B * Ho * Wo + 255 < 2 ** 31, "conv2d: B*Ho*Wo=%d output pixels exceed the 32-bit row index" % (B * Ho * Wo)
     d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
     d.kh, d.kw, d.sy, d.sx, d.py, d.px = kh, kw, stride, stride, py, px
     assert wp.shape[0] % nsub == 0
@@ -754,6 +756,7 @@ def head_points_launch(feat, inds, w1, b1, w2, b2, out, *, hc, J, K):
     `decode_launches`); w1: the four branches' `pack_head_points_weight` back to back; b1 [4*hc]; w2 [6+2J, hc] and b2 [6+2J]: the
     1x1 rows of wh, hps, reg, hp_offset; out: ONE storage of B*H*W*(6+2J) floats that holds the four NCHW maps back to back."""
     B, H, W, C = feat.shape
+    assert H * W < 2 ** 31 and B * H < 2 ** 31, "head_points: H*W=%d and B*H=%d must stay below 2^31 (32-bit plane and row indices)" % (H * W, B * H)
     assert tuple(inds.shape) == (B, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == B * H * W * (6 + 2 * J)
     assert w1.numel() == 4 * 9 * C * hc and b1.numel() == 4 * hc and tuple(w2.shape) == (6 + 2 * J, hc) and b2.numel() == 6 + 2 * J
     for t in (w1, b1, w2, b2):
@@ -768,6 +771,7 @@ def head_points_pairs_launch(feat, inds, perm, w1, b1, w2, b2, out, *, hc, J, K)
     for `head_points_launch`; out: ONE storage of N*H*W*(6+2J) floats that holds the four MERGED NCHW maps back to back."""
     N2, H, W, C = feat.shape
     N = N2 // 2
+    assert H * W < 2 ** 31 and N2 * H < 2 ** 31, "head_points_pairs: H*W=%d and 2*N*H=%d must stay below 2^31 (32-bit plane and row indices)" % (H * W, N2 * H)
     assert N2 % 2 == 0 and perm.dtype == torch.float32 and perm.is_contiguous() and perm.numel() == J
     assert tuple(inds.shape) == (N, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == N * H * W * (6 + 2 * J)
     assert w1.numel() == 4 * 9 * C * hc and b1.numel() == 4 * hc and tuple(w2.shape) == (6 + 2 * J, hc) and b2.numel() == 6 + 2 * J

@@ -40,7 +40,9 @@ enum { CP_ACT_NONE = 0, CP_ACT_RELU = 1, CP_ACT_SIGMOID = 2,
  * w: packed weights [ldw][K] (n-major, k contiguous), k = (ky*kw + kx)*Ctot + c  (inNCHW stem:
  * k = (c*kh + ky)*kw + kx, K padded to a multiple of 16 with zeros), ldw = Cout padded to 16 / 32 / a
  * multiple of 64 with zero rows;  3x3/s1/p1 single-source NHWC launches use the LDS halo-patch kernel;
- * scale/shift: [ldw] (folded BN or 1/bias).  res: NHWC residual with pixel stride resLd, or NULL. */
+ * scale/shift: [ldw] (folded BN or 1/bias).  res: NHWC residual with pixel stride resLd, or NULL.
+ * Size limits (32-bit device offsets; a larger problem is refused with rc 1): B*H*W < 2^31, B*Ho*Wo + 255 < 2^31, per NHWC source
+ * B*H*W*srcLd*4 < 2^32 bytes, and for the inNCHW source B*srcC[0]*H*W < 2^31 floats. */
 typedef struct cp_conv_desc {
     int nsrc;                 /* 1..4 sources */
     int srcC[4], srcLd[4];    /* channels taken from / pixel stride of each source (C % 16 == 0 unless inNCHW) */
@@ -255,7 +257,9 @@ int cp_decode_assign_f32(const float* wh, const float* kps, const float* reg, co
  * k = 8kb + 4h + s, k = tap * C + c (tap = ky * 3 + kx); b1: [4][hc]; w2: [6+2J][hc] = the 1x1 rows of wh (2), hps (2J), reg (2),
  * hp_offset (2); b2: [6+2J].  out: the four NCHW maps [B,n,H,W] back to back in that order (B*H*W*(6+2J) floats).  Writes every
  * channel of wh / hps / reg at every centre index and both hp_offset channels at every joint index, nothing else; a pixel's
- * values depend only on its 3x3 patch (duplicates are written with identical bits).  hc % 32 == 0, hc <= 512, C <= 512. */
+ * values depend only on its 3x3 patch (duplicates are written with identical bits).  hc % 32 == 0, hc <= 512, C <= 512.
+ * Size limits (32-bit plane and row indices; larger is refused with rc 1): H*W < 2^31, B*H < 2^31 (pairs: 2*N*H), B*(1+J)*K < 2^31,
+ * B*H*W*(6+2J) < 2^40. */
 int cp_head_points_f32(const float* feat, int featLd, const int* ws_inds, const float* w1, const float* b1, const float* w2,
                        const float* b2, float* out, int B, int H, int W, int C, int J, int K, int hc, void* stream);
 /* The same four branches under the flip test (multi_pose.py:45-53), at the peaks of the N MERGED heat maps.  feat: the head input of

@@ -265,11 +265,13 @@ def _sum_up(xs, shifts, relu):
     return Out(F.relu(v) if relu else v, A, len(ts))
 
 
-def dcn_stage(sd, x, om, conv, bn, co, dt):
+def dcn_stage(sd, x, om, conv, bn, co, dt, extent=None):
     """DCNv2 + bias + BN + ReLU from x and the given offset / mask logits `om` [B, 27, H, W] (teacher-forced: sampling is
     discontinuous in the offsets).  The sampling coordinate y + ky + offset is one float32 rounding away from its float64 value,
     <= u |coordinate| with |coordinate| < max(H, W) + 2 for every sample that contributes, and a bilinear sample moves by at most
-    (|dy| + |dx|) x 2 x the largest of its four corners: A carries P x the same DCN over the 3 x 3 max-pooled |x| (>= every corner)."""
+    (|dy| + |dx|) x 2 x the largest of its four corners: A carries P x the same DCN over the 3 x 3 max-pooled |x| (>= every corner).
+    extent: max(H, W) of the map the device launch samples when `x` is only a crop of it (tests/limit_oracle.py): the device forms its
+    coordinates in the whole map."""
     B, C, H, W = x.shape
     om = om.to(dt)
     off, mask = om[:, :18].contiguous(), torch.sigmoid(om[:, 18:27]).contiguous()
@@ -278,7 +280,7 @@ def dcn_stage(sd, x, om, conv, bn, co, dt):
     v = oracle_dcn.dcn_v2_forward_torch(x, w, None, off, mask) * scale + shift
     A = None
     if dt == torch.float64:
-        P = 2.0 * (max(H, W) + 2)
+        P = 2.0 * ((extent or max(H, W)) + 2)
         a = oracle_dcn.dcn_v2_forward_torch(x.abs() + P * F.max_pool2d(x.abs(), 3, 1, 1), w.abs(), None, off, mask)
         A = scale.abs() * a + ash
     return Out(F.relu(v), A, 9 * C + 4)
