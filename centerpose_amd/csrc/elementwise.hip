@@ -7,6 +7,7 @@
 //   depthwise conv + BN + act       MobileNetV3 Block.conv2 / ShuffleNetV2 banch*  mobilenetv3.py:119-121, shufflenetv2_dcn.py:67-88
 //   squeeze-excite                  SeModule: global average pool, x * se(x) (+ shortcut)  mobilenetv3.py:99-113,141-143
 //   channel shuffle of a concat     ShuffleNetV2 InvertedResidual.forward            shufflenetv2_dcn.py:28-42,94-104
+//   average pool + L2 normalise     re-id Net.forward tail                            demo/tracking/model.py:88-92
 #include <cstdlib>
 #include "common.h"
 
@@ -562,6 +563,49 @@ extern "C" int cp_global_avgpool_nhwc_f32(const float* in, int inLd, float* out,
                        out, outLd, HW, C / 4);
     cp_note_kernel("global_avgpool_kernel");
     CP_CHECK_LAUNCH("global_avgpool_kernel");
+    return 0;
+}
+
+// ---- global average pool + L2 normalisation: in [B, HW, C] -> out [B, C] = m / ||m||_2, m = mean over HW ------------------------
+// The tail of the DeepSort re-id net (demo/tracking/model.py:88-92: AvgPool2d over the whole map, x.div(x.norm(p=2, dim=1))); no
+// epsilon there, none here: an all-zero map gives NaN.  One block per image.  Thread t owns the channels t, t + 256, ...: it sums
+// their HW pixels in order (consecutive lanes read consecutive channels), divides by HW, parks the mean in `out` and keeps the
+// running sum of squares; the squares meet in a wave butterfly and a fixed-order sum of the four wave partials through LDS; every
+// thread then divides its own means by the root.  Fixed order throughout: the same input gives the same bits.
+__global__ __launch_bounds__(EW_THREADS) void pool_l2norm_kernel(const float* __restrict__ in, int inLd, float* __restrict__ out, int outLd,
+                                                                 int HW, int C)
+{
+    __shared__ float part[EW_THREADS / CP_WAVE];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* src = in + (size_t)b * HW * inLd;
+    float* dst = out + (size_t)b * outLd;
+    const float n = (float)HW;
+    float ss = 0.f;
+    for (int c = tid; c < C; c += EW_THREADS) {
+        float acc = 0.f;
+        for (int p = 0; p < HW; ++p) acc += src[(size_t)p * inLd + c];
+        const float m = acc / n;
+        dst[c] = m;
+        ss += m * m;
+    }
+#pragma unroll
+    for (int s = CP_WAVE / 2; s > 0; s >>= 1) ss += __shfl_xor(ss, s);
+    if (tid % CP_WAVE == 0) part[tid / CP_WAVE] = ss;
+    __syncthreads();
+    float tot = part[0];
+#pragma unroll
+    for (int w = 1; w < EW_THREADS / CP_WAVE; ++w) tot += part[w];
+    const float norm = sqrtf(tot);
+    for (int c = tid; c < C; c += EW_THREADS) dst[c] = dst[c] / norm;      // a thread re-reads only what it stored itself
+}
+
+extern "C" int cp_pool_l2norm_nhwc_f32(const float* in, int inLd, float* out, int outLd, int B, int HW, int C, void* stream)
+{
+    CP_CHECK_ARG(in && out && B > 0 && HW > 0 && B <= 65535, "pool_l2norm: bad arguments");
+    CP_CHECK_ARG(C > 0 && inLd >= C && outLd >= C, "pool_l2norm: inLd=%d and outLd=%d must be >= C=%d > 0", inLd, outLd, C);
+    hipLaunchKernelGGL(pool_l2norm_kernel, dim3((unsigned)B), dim3(EW_THREADS), 0, (hipStream_t)stream, in, inLd, out, outLd, HW, C);
+    cp_note_kernel("pool_l2norm_kernel");
+    CP_CHECK_LAUNCH("pool_l2norm_kernel");
     return 0;
 }
 

@@ -713,7 +713,7 @@ class BaseDetector(object):
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False):
+    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False, embed=None):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -731,10 +731,23 @@ class BaseDetector(object):
         list -- no download and no synchronisation; the tensor is ready in the current stream's order.
         draw=True (device frames only): once the rows are in input order the frames are painted with them, in place, as
         draw_results(images, rows, layout, color, matrix) does with the default threshold and style -- whose rules for writable frames
-        apply and are checked before anything is launched.  The return value is exactly what it is without `draw`."""
+        apply and are checked before anything is launched.  The return value is exactly what it is without `draw`.
+        embed=extractor (a reid.ReidExtractor; device frames only): -> (rows, result) with `rows` exactly what the call returns
+        without `embed` and `result` the extractor's ReidResult for the call's own rows, once they are in input order, at
+        TEST.VIS_THRESH -- what extractor.embed(images, rows, layout, color, matrix, vis_thresh=TEST.VIS_THRESH) gives.  With
+        draw=True as well the crops are taken before anything is painted.  More frames than the extractor's capacity: ValueError,
+        before anything is launched."""
         given = images
         images, frames = self._batch_input(images, layout, color, matrix)
         coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+        if embed is not None:
+            if frames is None:
+                raise ValueError("embed= takes its crops from frames on the device (CUDA uint8 tensors): host arrays are not read, "
+                                 "there is no CPU fallback")
+            if not 1 <= len(images) <= embed.capacity:
+                raise ValueError("%d frames for an extractor of capacity %d: every frame needs at least one slot" % (len(images), embed.capacity))
+            if embed.device != self._model_device():
+                raise _lib.CenterposeHipError("the extractor is on %s, the model is on %s" % (embed.device, self._model_device()))
         if draw:
             if frames is None and images:
                 raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -752,7 +765,7 @@ class BaseDetector(object):
                 work.append((table, scratch_bytes, inp_h, inp_w))
                 parts += [table, self._inverse_affines(metas)]
         order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
-        if (return_device or draw) and len(groups) > 1:
+        if (return_device or draw or embed is not None) and len(groups) > 1:
             parts.append(np.argsort(np.asarray(order, np.int64)).astype(np.int64))       # rides in the one table upload
         staging = self._upload_images(images, offsets, nbytes) if frames is None else None
         parts = self._upload_table(parts)
@@ -770,18 +783,20 @@ class BaseDetector(object):
                 per_scale.append(self._launch_post(dets, parts[2 * j + 1].view(torch.float64).view(1, len(idx), 6), scale))
             merged.append(self.merge_outputs_batch(per_scale))
         rows = merged[0] if len(merged) == 1 else torch.cat(merged, 0)
-        if draw:
+        ordered = result = None
+        if draw or return_device or embed is not None:
             ordered = rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
+        if embed is not None:                                    # from the frames as they were given: before anything is painted
+            result = embed._embed(frames, ordered.contiguous(), color, matrix, float(self.cfg.TEST.VIS_THRESH))
+        if draw:
             self._draw(images, frames, ordered, color, matrix, None, None)
-            if return_device:
-                return ordered
         if return_device:
-            return rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
+            return ordered if embed is None else (ordered, result)
         rows = rows.cpu().numpy()                                                               # the one download
         results = [None] * len(images)
         for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
-        return results
+        return results if embed is None else (results, result)
 
     @staticmethod
     def _check_writable(given, images, color):

@@ -364,6 +364,14 @@ class PlanBuilder(nets.Graph):
         mid = self.emit_conv([pooled], p + ".1", p + ".2", False, red, 1, 1, 0, True, None, False)
         return self.emit_conv([mid], p + ".4", p + ".5", False, x.C, 1, 1, 0, "hsigmoid", None, False)
 
+    def emit_pool_l2norm(self, x):
+        """The re-id net's tail (demo/tracking/model.py:88-92) as one launch: AvgPool2d over the whole map, then x / ||x||_2.  The
+        [B, C] result is the plan's only output."""
+        o = torch.empty((self.B, x.C), dtype=torch.float32, device=self.dev)
+        self.add("pool", "avgpool+l2norm", 0, ops.pool_l2norm_launch(x.t[..., :x.C], o))
+        self.outputs = [o]
+        return Act(1, 1, x.C, o.view(self.B, 1, 1, x.C))
+
     def emit_scale_add(self, x, se, add):
         out = self.buf(x.H, x.W, x.C)
         self.add("se", "se.scale", 0, ops.scale_add_launch(x.t, se.t, add.t if add is not None else None, out.t))
@@ -570,6 +578,9 @@ class Engine:
     def __init__(self, arch, state_dict, batch, height=512, width=512, device="cuda", head_conv=None,
                  sigmoid_heads=True, use_graph=True, decode_k=None, const_cache=None, sched_cache=None, dets_only=False,
                  flip_test=False, flip_dets_only=False):
+        if nets.canonical_arch(arch) == "reid" and (decode_k or dets_only or flip_test or flip_dets_only):
+            raise ValueError("arch 'reid' has no keypoint heads: decode_k, dets_only, flip_test and flip_dets_only do not apply "
+                             "(its plan returns [features], a [batch, %d] tensor)" % nets.REID_DIM)
         if flip_dets_only:
             # detections-only under the flip test: its own keyword (flip_test=True with dets_only=True keeps refusing below)
             if flip_test or dets_only:

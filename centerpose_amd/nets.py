@@ -15,6 +15,7 @@ Structure follows the reference modules (they are *not* imported):
   hrnet    lib/models/backbones/pose_higher_hrnet.py :98-235, :245-503 + experiments/hrnet_w32_512.yaml:63-130
   resdcn_N lib/models/backbones/resnet_dcn.py     BasicBlock :34-63, Bottleneck :66-103, PoseResNet :130-276 (N = 18 / 34 / 50 / 101)
   head     lib/models/heads/keypoint.py:14-42
+  reid     demo/tracking/model.py                 BasicBlock :6-38, make_layers :40-47, Net :49-93 (the DeepSort re-id net: no keypoint head)
 """
 from collections import OrderedDict
 
@@ -22,6 +23,7 @@ HEADS = (("hm", 1), ("wh", 2), ("hps", 34), ("reg", 2), ("hm_hp", 17), ("hp_offs
 # (INTERMEDIATE_CHANNEL, HEAD_CONV) per experiments/*.yaml
 ARCH_HEAD = {"dla_34": (64, 256), "res_50": (256, 64), "hrnet": (32, 64), "mobilenetv3": (24, 256), "shufflenetV2": (256, 256),
              "resdcn_18": (64, 64), "resdcn_34": (64, 64), "resdcn_50": (64, 64), "resdcn_101": (64, 64)}
+REID_INPUT, REID_DIM = (128, 64), 512                             # demo/tracking/model.py:52, :69
 RESDCN_SPEC = {18: ("basic", [2, 2, 2, 2]), 34: ("basic", [3, 4, 6, 3]), 50: ("bottleneck", [3, 4, 6, 3]),
                101: ("bottleneck", [3, 4, 23, 3])}                       # resnet_dcn.py:270-274
 
@@ -92,6 +94,9 @@ class Graph:
 
     def emit_head(self, feat, p, hc):
         return None
+
+    def emit_pool_l2norm(self, x):
+        return Act(1, 1, x.C)
 
     def emit_dwconv(self, x, conv, bn, k, stride, act):
         return Act((x.H + 2 * (k // 2) - k) // stride + 1, (x.W + 2 * (k // 2) - k) // stride + 1, x.C, split=x.split)
@@ -424,6 +429,30 @@ class Graph:
             self.flops += 2 * x_in.H * x_in.W * 256 * 256 * 16
         return x
 
+    # ---- DeepSort re-id net: no keypoint head, un-prefixed keys ----------------------------------------
+    def reid(self, x):
+        """Net(reid=True).forward, demo/tracking/model.py:82-93: 3x3 stem conv (bias) + BN + ReLU + 3x3/s2 max-pool, layer1..4 of two
+        BasicBlocks each (downsample = 1x1/s2 conv + BN in the first block of layer2..4, :18-22), AvgPool2d((8, 4)) over the whole 8 x 4
+        map, x / ||x||_2.  The input is the fixed 3 x 128 x 64 crop (:52): the pool window is the map only at that size."""
+        if (x.H, x.W) != REID_INPUT:
+            raise ValueError("arch 'reid' takes 3 x %d x %d crops only (got %d x %d)" % (REID_INPUT + (x.H, x.W)))
+        x = self.conv(x, "conv.0", "conv.1", 64, 3, 1, 1, relu=True, bias=True, stem=True)
+        x = self.emit_maxpool(x, 3, 2, 1)
+        for li, (planes, down) in enumerate(zip([64, 128, 256, 512], [False, True, True, True]), start=1):
+            for b in range(2):
+                q = "layer%d.%d" % (li, b)
+                s = 2 if (down and b == 0) else 1
+                res = x
+                for cv, bn, ci in ((".conv1", ".bn1", x.C), (".conv2", ".bn2", planes)):    # key order of the module: downsample.* last
+                    self.p_conv(q + cv, planes, ci, 3)
+                    self.p_bn(q + bn, planes)
+                if s == 2:
+                    res = self.conv(x, q + ".downsample.0", q + ".downsample.1", planes, 1, 2, 0)
+                h = self.conv(x, q + ".conv1", q + ".bn1", planes, 3, s, 1, relu=True)
+                x = self.conv(h, q + ".conv2", q + ".bn2", planes, 3, 1, 1, relu=True, res=res)
+        assert (x.H, x.W, x.C) == (8, 4, REID_DIM)
+        return self.emit_pool_l2norm(x)
+
     # ---- head --------------------------------------------------------------------------------
     def head(self, feat, hc, p="head_model"):
         for h, n in HEADS:
@@ -434,6 +463,8 @@ class Graph:
 
     def network(self, arch, x, head_conv=None):
         base = canonical_arch(arch)
+        if base == "reid":                                            # no keypoint head: the plan ends in the embedding
+            return self.reid(x)
         inter, hc = ARCH_HEAD[base]
         if base.startswith("resdcn_"):
             feat = self.resdcn(x, int(base.split("_")[1]))
@@ -461,8 +492,10 @@ def canonical_arch(arch):
         n = a.replace("resdcn", "").strip("_") or "18"
         if n.isdigit() and int(n) in RESDCN_SPEC:
             return "resdcn_%d" % int(n)
+    if a == "reid":                                              # demo/tracking/model.py Net(reid=True): not a cfg.MODEL.NAME
+        return "reid"
     raise ValueError("unsupported arch %r (the MI355X hot path covers dla_34, res_50, hrnet, mobilenetv3, shufflenetV2, "
-                     "resdcn_18/34/50/101)" % arch)
+                     "resdcn_18/34/50/101 and the re-id net reid)" % arch)
 
 
 _HEAD_NAMES = tuple(h for h, _ in HEADS)
@@ -471,8 +504,9 @@ _HEAD_NAMES = tuple(h for h, _ in HEADS)
 def internal_key(arch, k):
     """checkpoint key -> the graph's key.  Every model built by BackBoneWithHead already has `backbone_model.` / `head_model.`
     prefixes (model.py:44-59); `resdcn` is a stand-alone PoseResNet whose keys have none (conv1.weight, hm.0.weight, ...)."""
-    if not canonical_arch(arch).startswith("resdcn_") or k.startswith(("backbone_model.", "head_model.")):
-        return k
+    base = canonical_arch(arch)
+    if not base.startswith("resdcn_") or k.startswith(("backbone_model.", "head_model.")):
+        return k                                                 # (reid: the module's own keys, no prefix on either side)
     return ("head_model." if k.split(".", 1)[0] in _HEAD_NAMES else "backbone_model.") + k
 
 
@@ -486,9 +520,11 @@ def reference_key(arch, k):
     return k
 
 
-def param_spec(arch, H=512, W=512, head_conv=None, internal=False):
+def param_spec(arch, H=None, W=None, head_conv=None, internal=False):
     """OrderedDict name -> shape of the reference checkpoint for `arch`, plus algorithmic FLOPs/image.  Names are the
-    reference's (`reference_key`) unless `internal`."""
+    reference's (`reference_key`) unless `internal`.  H, W default to 512 x 512 (reid: its fixed 128 x 64 crop)."""
+    dh, dw = REID_INPUT if canonical_arch(arch) == "reid" else (512, 512)
+    H, W = dh if H is None else H, dw if W is None else W
     g = Graph()
     g.network(arch, Act(H, W, 3), head_conv)
     if internal:

@@ -105,7 +105,7 @@ def marshal(fn, desc, ptrs, ints):
         return [ints[0], srcs, meta, outs, ints[1]]
     if fn == "cp_dwconv2d_nhwc_f32":              # ptrs: in, w, scale, shift, out; ints: inLd, outLd, B, H, W, C, k, s, p, act
         return [ptrs[0], ints[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4]] + ints[1:]
-    if fn == "cp_global_avgpool_nhwc_f32":        # ptrs: in, out; ints: inLd, outLd, B, HW, C
+    if fn in ("cp_global_avgpool_nhwc_f32", "cp_pool_l2norm_nhwc_f32"):       # ptrs: in, out; ints: inLd, outLd, B, HW, C
         return [ptrs[0], ints[0], ptrs[1]] + ints[1:]
     if fn == "cp_scale_add_nhwc_f32":             # ptrs: x, se, add, out; ints: xLd, seLd, addLd, outLd, B, H, W, C
         return [ptrs[0], ints[0], ptrs[1], ints[1], ptrs[2], ints[2], ptrs[3]] + ints[3:]
@@ -135,6 +135,8 @@ FN_IDS = {"cp_conv2d_f32": 1, "cp_conv3x3_winograd_f32": 2, "cp_dcn_v2_f32": 3, 
           "cp_decode_topk_f32": 13, "cp_decode_assign_f32": 14, "cp_splitk_reduce_f32": 15, "cp_conv3x3_winograd24_group_f32": 16, "cp_conv2d_group_f32": 17,
           "cp_sum_up_group_nhwc_f32": 18, "cp_head_points_f32": 19,
           "cp_flip_merge_pairs_f32": 20, "cp_head_points_pairs_f32": 21}
+# (cp_pool_l2norm_nhwc_f32, the tail of the re-id plan, is marshalled above but has no id: a plan file is the detector's format and
+# plan.save_plan refuses arch "reid"; an id here needs its row in the C dispatcher and in the schedule audit's write table with it)
 
 
 def pad_rows(t, ldw):
@@ -605,6 +607,18 @@ def global_avgpool_launch(x, out):
 
 def global_avgpool(x, out):
     global_avgpool_launch(x, out).run()
+    return out
+
+
+def pool_l2norm_launch(x, out):
+    """x NHWC [B,H,W,C] (pixel stride >= C) -> out [B, >= C]: the mean over H*W, divided by its L2 norm over C (no epsilon)."""
+    B, H, W, C = x.shape
+    assert out.dim() == 2 and out.shape[0] == B and out.shape[1] >= C and out.stride(1) == 1
+    return Launch("cp_pool_l2norm_nhwc_f32", None, [x, out], [_ld(x), out.stride(0), B, H * W, C])
+
+
+def pool_l2norm(x, out):
+    pool_l2norm_launch(x, out).run()
     return out
 
 

@@ -157,6 +157,10 @@ def plan_blob(engine, deterministic=False):
     when it has not captured yet (it will then capture the same order), computed on the side when a graph already exists (an
     engine captured with CP_STREAMS=1 / CP_SCHED=0 keeps its launch order, `stream_of_launch` and profile indices: ADVICE r2)."""
     import os
+    if getattr(engine, "arch", None) == "reid":
+        # a plan file is the detector's format: six head outputs, and the C runtime's dispatcher has no cp_pool_l2norm_nhwc_f32
+        raise ValueError("arch 'reid' cannot be written to a plan file: the C plan runtime does not run the re-id plan "
+                         "(build it with Engine('reid', state_dict, ...) / reid.ReidExtractor instead)")
     launches, streams = engine.launches, getattr(engine, "stream_plan", None)
     can_schedule = os.environ.get("CP_SCHED", "1") != "0" and os.environ.get("CP_STREAMS", "2") == "2"
     if deterministic:

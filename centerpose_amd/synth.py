@@ -30,6 +30,8 @@ def _feeds_residual_add(name, arch=""):
     """BN whose output is summed with a skip / other branches (gamma scaled down)."""
     if arch in ("resdcn_18", "resdcn_34") and ".layer" in name and name.endswith(".bn2.weight"):
         return True                                                   # BasicBlock.bn2 (resnet_dcn.py:52-63)
+    if arch == "reid":
+        return name.startswith("layer") and name.endswith(".bn2.weight")      # BasicBlock.bn2 (demo/tracking/model.py:34-38)
     if name in ("backbone_model.bn2.weight",):                        # hrnet stem bn2: plain conv-bn-relu
         return False
     if name.endswith((".bn2.weight", ".bn3.weight")) and (".tree" in name or ".layer" in name or ".branches." in name):
@@ -44,7 +46,7 @@ def _feeds_residual_add(name, arch=""):
 
 # empirical damping of the remaining BN gammas so that activations stay O(1) through depth
 GAMMA_DAMP = {"dla_34": 0.8, "res_50": 0.75, "hrnet": 0.62, "mobilenetv3": 0.8, "shufflenetV2": 0.65,
-              "resdcn_18": 0.85, "resdcn_34": 0.85, "resdcn_50": 0.75, "resdcn_101": 0.75}
+              "resdcn_18": 0.85, "resdcn_34": 0.85, "resdcn_50": 0.75, "resdcn_101": 0.75, "reid": 0.85}
 
 HEAD_TARGET = {  # final 1x1 layer: (output std, bias)
     "hm": (3.0, -1.0), "wh": (4.0, 12.0), "hps": (8.0, 0.0), "reg": (0.2, 0.5), "hm_hp": (3.0, -1.5),
@@ -52,7 +54,7 @@ HEAD_TARGET = {  # final 1x1 layer: (output std, bias)
 }
 
 
-def make_state_dict(arch, seed=317, head_conv=None, H=512, W=512):
+def make_state_dict(arch, seed=317, head_conv=None, H=None, W=None):
     """dict name -> torch.float32 tensor (CPU) with the reference key names for `arch`."""
     spec, _ = nets.param_spec(arch, H, W, head_conv, internal=True)
     arch = nets.canonical_arch(arch)

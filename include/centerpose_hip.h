@@ -187,6 +187,10 @@ int cp_dwconv2d_nhwc_f32(const float* in, int inLd, const float* w, const float*
 int cp_global_avgpool_nhwc_f32(const float* in, int inLd, float* out, int outLd, int B, int HW, int C, void* stream);
 int cp_scale_add_nhwc_f32(const float* x, int xLd, const float* se, int seLd, const float* add, int addLd, float* out, int outLd,
                           int B, int H, int W, int C, void* stream);
+/* The tail of the DeepSort re-id net (demo/tracking/model.py:88-92: AvgPool2d over the whole map, x.div(x.norm(p=2, dim=1))):
+ * in [B,HW,C] (pixel stride inLd >= C) -> out [B,C] (row stride outLd >= C) = m / ||m||_2 with m the mean over HW.  No epsilon, as
+ * there: an all-zero map gives NaN.  One block per image, fixed summation order; B <= 65535. */
+int cp_pool_l2norm_nhwc_f32(const float* in, int inLd, float* out, int outLd, int B, int HW, int C, void* stream);
 /* channel_shuffle(torch.cat((x1, x2), 1), 2) of ShuffleNetV2 (shufflenetv2_dcn.py:28-42,94-104); x1, x2: h channels each;
  * out: two halves of hp (>= h, multiple of 16) physical channels, logical channel c -> c (c < h) or hp + c - h; pads = 0 */
 int cp_shuffle_concat_nhwc_f32(const float* x1, int ld1, const float* x2, int ld2, float* out, int outLd, long long npix, int h, int hp,
@@ -486,6 +490,53 @@ int cp_draw_rows_yuv_frames_u8(const void* table, const void* table_host, int N,
                                const void* style, void* scratch, size_t scratch_bytes, void* stream);
 int cp_draw_rows_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
 int cp_draw_rows_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
+
+/* ---- re-id crops: detections cut out of device frames into the re-id plan's input (reid.ReidExtractor / run_batch(embed=)) -------------
+ * What DeepSort._get_features + Extractor._preprocess do per box on the host (demo/tracking/deep_sort.py:66-86,
+ * feature_extractor.py:15-39), for every row of rows[N,M,56] and its own frame n, in two launches.  The values are this library's own
+ * statement of that pipeline (csrc/reid_arith.h), not pinned to a cv2 recording:
+ *   box: row = [x1, y1, x2, y2, score, ...]; the coordinates are clamped to +-2^30 and truncated toward zero; w = x2 - x1, h = y2 - y1,
+ *     X1 = max(x1, 0), Y1 = max(y1, 0), X2 = min(X1 + w, W - 1), Y2 = min(Y1 + h, H - 1); the crop is rows Y1..Y2-1, columns X1..X2-1.
+ *     A row is selected iff score > vis_thresh (strict; NaN is not), no coordinate is NaN and the crop has pixels.
+ *   slots: with q = cap / N the first q selected rows of frame n, in row order, take slots n * q + 0, 1, ...
+ *   pixel (oy, ox) of a crop of cw x ch pixels: fx = (ox + 0.5) * (cw / 64) - 0.5 in double, sx = floor(fx), weight f = float(fx - sx);
+ *     sx < 0: column 0 alone, sx >= cw - 1: column cw - 1 alone, else columns sx, sx + 1 with float weights (1 - f, f); rows alike with
+ *     ch / 128.  The four 8-bit taps are blended horizontally, then vertically, in double, rounded to float; then, in float,
+ *     (v * scale - mean[k]) / std_[k].  Output channel k reads the frame's channel k of (B, G, R), or 2 - k with rgb = 1.
+ * cp_reid_norm (HOST): scale, mean[3], std_[3], rgb.  The reference's values: scale 1 (its / 255 is commented out), mean (0.485, 0.456,
+ *   0.406), std (0.229, 0.224, 0.225), rgb 0.
+ * cp_reid_select_rows: one wave per frame -> slots[cap] DEVICE int (n * M + m, or -1 for an unused slot) and counts[N] DEVICE int (the
+ *   selected rows per frame, NOT capped at q: a caller sees overflow without a synchronisation here).  table: DEVICE cp_frame_desc[N]
+ *   (yuv = 0) or cp_yuv_frame_desc[N] (yuv = 1), table_host: the same on the HOST; only H and W are read.  rows: DEVICE float32 [N,M,56].
+ * cp_reid_crop_frames_f32 / cp_reid_crop_yuv_frames_f32: out DEVICE float32 [cap,3,128,64], every element written: slot s holds the
+ *   crop of row slots[s], zeros where slots[s] is -1 (or out of range, or not a selected row).  One thread per output pixel, frames
+ *   read in place through the descriptors (addressing fields, H, W), YUV frames converted per source pixel with nearest chroma as in
+ *   cp_preprocess_yuv_frames_u8_f32 (coef: HOST int[6], same rule).
+ *   Checked before anything is launched (rc 1, cp_last_error): null pointers, cap in 1..4096, 1 <= N <= cap, M >= 0, N * M <= 2^24, and
+ *   per frame: bases non-null, H, W positive and below 2^29 pixels, no negative stride or offset, addressed offsets below 2^62.  The
+ *   caller vouches for the frames' memory, stream order and lifetime as for the pre-process; frames are only read, so expanded and
+ *   overlapping views are fine.  cp_last_kernel(): reid_select_kernel<bgr|yuv>, reid_crop_kernel<bgr|yuv>.
+ * cp_reid_*_host: HOST only -- sequential twins over descriptors holding host addresses, host rows / slots / out, built from the same
+ *   statements; same checks.  What the device results are pinned to, bit for bit. */
+typedef struct cp_reid_norm {       /* 32 bytes */
+    float scale;
+    float mean[3];
+    float std_[3];
+    int rgb;
+} cp_reid_norm;
+int cp_sizeof_reid_norm(void);
+int cp_reid_select_rows(const void* table, const void* table_host, int yuv, int N, const float* rows, int M, float vis_thresh, int cap,
+                        int* slots, int* counts, void* stream);
+int cp_reid_crop_frames_f32(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                            const int* slots, int cap, const void* norm, float* out, void* stream);
+int cp_reid_crop_yuv_frames_f32(const void* table, const void* table_host, int N, const int* coef, const float* rows, int M,
+                                float vis_thresh, const int* slots, int cap, const void* norm, float* out, void* stream);
+int cp_reid_select_rows_host(const void* table_host, int yuv, int N, const float* rows, int M, float vis_thresh, int cap, int* slots,
+                             int* counts);
+int cp_reid_crop_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const int* slots, int cap,
+                             const void* norm, float* out);
+int cp_reid_crop_yuv_frames_host(const void* table_host, int N, const int* coef, const float* rows, int M, float vis_thresh,
+                                 const int* slots, int cap, const void* norm, float* out);
 
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
