@@ -20,6 +20,10 @@
 
 typedef float hp_f32x16 __attribute__((ext_vector_type(16)));
 
+// hidden tiles per wave (the kernels' NS) and the block size of a launch: one wave per NS 32-wide hidden column tiles
+static inline int hp_tiles_per_wave(int hc) { return (hc % 64 == 0 && hc >= 128) ? 2 : 1; }
+static inline int hp_block_threads(int hc) { return 64 * hc / (32 * hp_tiles_per_wave(hc)); }
+
 // w1: per branch [9C/8][2][hc][4]: element (kb, h, n, s) = weight of hidden channel n at k = 8 kb + 4 h + s (k = tap * C + c);
 // lane half h of MFMA step s of k-group kb multiplies A[point][8 kb + 4 h + s] by B[8 kb + 4 h + s][n], so both operands of a
 // k-group are one float4 per lane.  b1: [4][hc].  w2: [6 + 2J][hc] rows of wh (2), hps (2J), reg (2), hp_offset (2); b2 alike.
@@ -250,12 +254,15 @@ extern "C" int cp_head_points_f32(const float* feat, int featLd, const int* ws_i
     CP_CHECK_ARG(C > 0 && C % 16 == 0 && C <= 512, "head_points: C=%d must be a multiple of 16 in 16..512 (physical channels)", C);
     CP_CHECK_ARG(featLd >= C && featLd % 4 == 0 && ((size_t)feat & 15) == 0, "head_points: feat must be 16-B aligned with ld %% 4 == 0 (ld %d)", featLd);
     CP_CHECK_ARG(hc > 0 && hc % 32 == 0 && hc <= 512, "head_points: head_conv=%d must be a multiple of 32 up to 512", hc);
+    // a wave takes two 32-wide hidden tiles only when hc is a multiple of 64: an odd multiple of 32 above 256 would need 576 .. 960 threads
+    CP_CHECK_ARG(hp_block_threads(hc) <= 512, "head_points: head_conv=%d needs a block of %d threads, the kernel takes 512 at most "
+                 "(served: multiples of 32 up to 256, multiples of 64 up to 512)", hc, hp_block_threads(hc));
     CP_CHECK_ARG((long long)B * (1 + J) * K < (1ll << 31) && (long long)B * H * W * (6 + 2 * J) < (1ll << 40), "head_points: too large");
     // the kernel keeps H * W, a point's plane index and the pixel row b * H + y in `int`
     CP_CHECK_ARG((long long)H * W < (1ll << 31) && (long long)B * H < (1ll << 31),
                  "head_points: too large: H*W=%lld and B*H=%lld must stay below 2^31 (32-bit plane and row indices)", (long long)H * W, (long long)B * H);
-    const int ns = (hc % 64 == 0 && hc >= 128) ? 2 : 1;
-    const int nthr = 64 * hc / (32 * ns);
+    const int ns = hp_tiles_per_wave(hc);
+    const int nthr = hp_block_threads(hc);
     const int nct = cp_cdiv(B * K, HP_M), njt = cp_cdiv(B * J * K, HP_M);
     const size_t lds = (size_t)HP_M * (C + 4) * 4 + (size_t)HP_M * (hc + 1) * 4;
     static CpLdsGuard lds_reserved[2];
@@ -286,11 +293,13 @@ extern "C" int cp_head_points_pairs_f32(const float* feat, int featLd, const int
     CP_CHECK_ARG(C > 0 && C % 16 == 0 && C <= 512, "head_points_pairs: C=%d must be a multiple of 16 in 16..512 (physical channels)", C);
     CP_CHECK_ARG(featLd >= C && featLd % 4 == 0 && ((size_t)feat & 15) == 0, "head_points_pairs: feat must be 16-B aligned with ld %% 4 == 0 (ld %d)", featLd);
     CP_CHECK_ARG(hc > 0 && hc % 32 == 0 && hc <= 512, "head_points_pairs: head_conv=%d must be a multiple of 32 up to 512", hc);
+    CP_CHECK_ARG(hp_block_threads(hc) <= 512, "head_points_pairs: head_conv=%d needs a block of %d threads, the kernel takes 512 at most "
+                 "(served: multiples of 32 up to 256, multiples of 64 up to 512)", hc, hp_block_threads(hc));
     CP_CHECK_ARG((long long)N * (1 + J) * K < (1ll << 31) && (long long)2 * N * H * W * (6 + 2 * J) < (1ll << 40) && (long long)2 * N * H < (1ll << 31),
                  "head_points_pairs: too large");
     CP_CHECK_ARG((long long)H * W < (1ll << 31), "head_points_pairs: too large: H*W=%lld must stay below 2^31 (32-bit plane index)", (long long)H * W);
-    const int ns = (hc % 64 == 0 && hc >= 128) ? 2 : 1;
-    const int nthr = 64 * hc / (32 * ns);
+    const int ns = hp_tiles_per_wave(hc);
+    const int nthr = hp_block_threads(hc);
     const int nct = cp_cdiv(N * K, HP_M), njt = cp_cdiv(N * J * K, HP_M);
     const size_t lds = (size_t)HP_M * (C + 4) * 4 + (size_t)HP_M * (hc + 1) * 4 + (size_t)HP_M * 2 * J * 4;
     static CpLdsGuard lds_reserved[2];

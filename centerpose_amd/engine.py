@@ -477,8 +477,9 @@ class PlanBuilder(nets.Graph):
     def head_points_consts(self, feat, p, hc):
         """The SPARSE_HEADS branches as the packed constants of cp_head_points_f32 (same checkpoint tensors as the dense launches):
         dict(feat, hc, w1, b1, w2, b2)."""
-        if hc % 32 or hc > 512 or feat.t.shape[3] > 512:
-            raise ValueError("dets_only: the points kernel needs head_conv % 32 == 0 and <= 512 (got %d) and <= 512 head input channels" % hc)
+        if ops.check_head_points_hc(hc, "dets_only") or feat.t.shape[3] > 512:
+            raise ValueError("dets_only: the points kernel needs head_conv to be a multiple of 32 up to 256 or a multiple of 64 up to 512 "
+                             "(got %d: %s) and <= 512 head input channels" % (hc, ops.check_head_points_hc(hc, "dets_only") or "served"))
         w1 = torch.cat([ops.pack_head_points_weight(self.expand_in(self.w("%s.%s.0.weight" % (p, h)), [feat])) for h in SPARSE_HEADS])
         b1 = torch.cat([self.w("%s.%s.0.bias" % (p, h)).float() for h in SPARSE_HEADS]).contiguous()
         w2 = torch.cat([self.w("%s.%s.2.weight" % (p, h)).reshape(-1, hc).float() for h in SPARSE_HEADS]).contiguous()

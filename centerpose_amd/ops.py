@@ -764,12 +764,32 @@ def pack_head_points_weight(w3):
     return wk.permute(0, 1, 3, 2).contiguous().reshape(-1)
 
 
+def head_points_block(hc):
+    """(hidden tiles per wave, threads per block) of the points kernels for `hc` hidden channels, as csrc/head_points.hip sizes them:
+    one wave per tile, two tiles per wave only for multiples of 64 from 128.  The kernels take 512 threads at most, which serves the
+    multiples of 32 up to 256 and the multiples of 64 up to 512 (288, 352, 416 and 480 would need 576 .. 960 threads)."""
+    ns = 2 if hc % 64 == 0 and hc >= 128 else 1
+    return ns, 64 * hc // (32 * ns)
+
+
+def check_head_points_hc(hc, what):
+    """the launchers' own refusal, before a record is built: -> the message, or None when `hc` is served"""
+    if hc <= 0 or hc % 32 or hc > 512:
+        return "%s: head_conv=%d must be a multiple of 32 up to 512" % (what, hc)
+    nthr = head_points_block(hc)[1]
+    if nthr > 512:
+        return ("%s: head_conv=%d needs a block of %d threads, the kernel takes 512 at most (served: multiples of 32 up to 256, "
+                "multiples of 64 up to 512)" % (what, hc, nthr))
+    return None
+
+
 def head_points_launch(feat, inds, w1, b1, w2, b2, out, *, hc, J, K):
     """wh / hps / reg at the centre peaks and hp_offset at the joint peaks (cp_head_points_f32) as one launch record.  feat: the head
     input NHWC [B,H,W,C physical]; inds: the peak extraction's flat indices [B,1+J,K] (the int32 bit patterns in float32, ws[1] of
     `decode_launches`); w1: the four branches' `pack_head_points_weight` back to back; b1 [4*hc]; w2 [6+2J, hc] and b2 [6+2J]: the
     1x1 rows of wh, hps, reg, hp_offset; out: ONE storage of B*H*W*(6+2J) floats that holds the four NCHW maps back to back."""
     B, H, W, C = feat.shape
+    assert check_head_points_hc(hc, "head_points") is None, check_head_points_hc(hc, "head_points")
     assert H * W < 2 ** 31 and B * H < 2 ** 31, "head_points: H*W=%d and B*H=%d must stay below 2^31 (32-bit plane and row indices)" % (H * W, B * H)
     assert tuple(inds.shape) == (B, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == B * H * W * (6 + 2 * J)
     assert w1.numel() == 4 * 9 * C * hc and b1.numel() == 4 * hc and tuple(w2.shape) == (6 + 2 * J, hc) and b2.numel() == 6 + 2 * J
@@ -785,6 +805,7 @@ def head_points_pairs_launch(feat, inds, perm, w1, b1, w2, b2, out, *, hc, J, K)
     for `head_points_launch`; out: ONE storage of N*H*W*(6+2J) floats that holds the four MERGED NCHW maps back to back."""
     N2, H, W, C = feat.shape
     N = N2 // 2
+    assert check_head_points_hc(hc, "head_points_pairs") is None, check_head_points_hc(hc, "head_points_pairs")
     assert H * W < 2 ** 31 and N2 * H < 2 ** 31, "head_points_pairs: H*W=%d and 2*N*H=%d must stay below 2^31 (32-bit plane and row indices)" % (H * W, N2 * H)
     assert N2 % 2 == 0 and perm.dtype == torch.float32 and perm.is_contiguous() and perm.numel() == J
     assert tuple(inds.shape) == (N, 1 + J, K) and inds.is_contiguous() and out.is_contiguous() and out.numel() == N * H * W * (6 + 2 * J)

@@ -261,7 +261,8 @@ int cp_decode_assign_f32(const float* wh, const float* kps, const float* reg, co
  * k = 8kb + 4h + s, k = tap * C + c (tap = ky * 3 + kx); b1: [4][hc]; w2: [6+2J][hc] = the 1x1 rows of wh (2), hps (2J), reg (2),
  * hp_offset (2); b2: [6+2J].  out: the four NCHW maps [B,n,H,W] back to back in that order (B*H*W*(6+2J) floats).  Writes every
  * channel of wh / hps / reg at every centre index and both hp_offset channels at every joint index, nothing else; a pixel's
- * values depend only on its 3x3 patch (duplicates are written with identical bits).  hc % 32 == 0, hc <= 512, C <= 512.
+ * values depend only on its 3x3 patch (duplicates are written with identical bits).  C <= 512; hc a multiple of 32 up to 256 or a multiple of 64 up to 512 (a block of
+ * 2 hc resp. hc threads, 512 at most: hc = 288, 352, 416 and 480 are refused with rc 1).
  * Size limits (32-bit plane and row indices; larger is refused with rc 1): H*W < 2^31, B*H < 2^31 (pairs: 2*N*H), B*(1+J)*K < 2^31,
  * B*H*W*(6+2J) < 2^40. */
 int cp_head_points_f32(const float* feat, int featLd, const int* ws_inds, const float* w1, const float* b1, const float* w2,

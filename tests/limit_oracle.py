@@ -283,14 +283,14 @@ def checks_tier2(kind, w=32, fixed=True, **p):
     else:
         pairs = kind == "head_points_pairs"
         n = p["N"]
-        add("rows", "head_points.hip:253", n * (1 + p["J"]) * p["K"], half)
-        add("map elements", "head_points.hip:253", (2 if pairs else 1) * n * p["H"] * p["W"] * (6 + 2 * p["J"]), 1 << (w + 8))
+        add("rows", "head_points.hip:260", n * (1 + p["J"]) * p["K"], half)
+        add("map elements", "head_points.hip:260", (2 if pairs else 1) * n * p["H"] * p["W"] * (6 + 2 * p["J"]), 1 << (w + 8))
         if pairs:
-            add("2*N*H", "head_points.hip:290", 2 * n * p["H"], half)
+            add("2*N*H", "head_points.hip:298", 2 * n * p["H"], half)
         if fixed:
-            add("H*W", "head_points.hip:255", p["H"] * p["W"], half)
+            add("H*W", "head_points.hip:262", p["H"] * p["W"], half)
             if not pairs:
-                add("B*H", "head_points.hip:255", n * p["H"], half)
+                add("B*H", "head_points.hip:262", n * p["H"], half)
     return out
 
 
@@ -308,9 +308,9 @@ def audit_tier2(kind, w=32, **p):
         add("t", "flip_pairs.hip:27", "int", 0, cdiv(n, 256) * 256 - 1)
     else:
         pairs = kind == "head_points_pairs"
-        add("HW = H*W", "head_points.hip:36", "int", p["H"] * p["W"], p["H"] * p["W"])
-        add("(b*H + yy)", "head_points.hip:74", "int", -1, (2 if pairs else 1) * p["N"] * p["H"])
-        add("B*J*K", "head_points.hip:259", "int", 0, p["N"] * p["J"] * p["K"])
+        add("HW = H*W", "head_points.hip:40", "int", p["H"] * p["W"], p["H"] * p["W"])
+        add("(b*H + yy)", "head_points.hip:78", "int", -1, (2 if pairs else 1) * p["N"] * p["H"])
+        add("B*J*K", "head_points.hip:266", "int", 0, p["N"] * p["J"] * p["K"])
     return q
 
 
