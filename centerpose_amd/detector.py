@@ -713,7 +713,8 @@ class BaseDetector(object):
     def merge_outputs_batch(self, detections):
         raise NotImplementedError
 
-    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False, embed=None):
+    def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False, embed=None,
+                  track=None):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -736,7 +737,11 @@ class BaseDetector(object):
         without `embed` and `result` the extractor's ReidResult for the call's own rows, once they are in input order, at
         TEST.VIS_THRESH -- what extractor.embed(images, rows, layout, color, matrix, vis_thresh=TEST.VIS_THRESH) gives.  With
         draw=True as well the crops are taken before anything is painted.  More frames than the extractor's capacity: ValueError,
-        before anything is launched."""
+        before anything is launched.
+        track=tracker (a track.DeepSortTracker; needs embed=): -> (rows, result, tracks) with `rows` and `result` exactly what the call
+        returns without `track` and `tracks` = tracker.update(rows, result, sizes) on the call's own rows in input order, frame n being
+        stream n: a list of int64 [k, 5] arrays (x1, y1, x2, y2, track_id).  Taken before draw=True paints.  The tracker's download is
+        a synchronisation of its own.  Without embed=, or with len(images) != tracker.streams: ValueError, before anything is launched."""
         given = images
         images, frames = self._batch_input(images, layout, color, matrix)
         coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
@@ -748,6 +753,15 @@ class BaseDetector(object):
                 raise ValueError("%d frames for an extractor of capacity %d: every frame needs at least one slot" % (len(images), embed.capacity))
             if embed.device != self._model_device():
                 raise _lib.CenterposeHipError("the extractor is on %s, the model is on %s" % (embed.device, self._model_device()))
+        if track is not None:
+            if embed is None:
+                raise ValueError("track= needs embed=: the tracker matches the extractor's features")
+            if len(images) != track.streams:
+                raise ValueError("%d frames for a tracker of %d streams: frame n of a call belongs to stream n" % (len(images), track.streams))
+            if track.capacity != embed.capacity:
+                raise ValueError("the tracker was built for capacity %d, the extractor has %d" % (track.capacity, embed.capacity))
+            if track.device != embed.device:
+                raise _lib.CenterposeHipError("the tracker is on %s, the extractor is on %s" % (track.device, embed.device))
         if draw:
             if frames is None and images:
                 raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -788,15 +802,18 @@ class BaseDetector(object):
             ordered = rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
         if embed is not None:                                    # from the frames as they were given: before anything is painted
             result = embed._embed(frames, ordered.contiguous(), color, matrix, float(self.cfg.TEST.VIS_THRESH))
+        tracks = None
+        if track is not None:                                    # before anything is painted, like the crops
+            tracks = track.update(ordered, result, [(int(w), int(h)) for h, w in shapes])
         if draw:
             self._draw(images, frames, ordered, color, matrix, None, None)
         if return_device:
-            return ordered if embed is None else (ordered, result)
+            return ordered if embed is None else (ordered, result) if track is None else (ordered, result, tracks)
         rows = rows.cpu().numpy()                                                               # the one download
         results = [None] * len(images)
         for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
-        return results if embed is None else (results, result)
+        return results if embed is None else (results, result) if track is None else (results, result, tracks)
 
     @staticmethod
     def _check_writable(given, images, color):

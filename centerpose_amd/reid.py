@@ -5,8 +5,8 @@ Replaces the hot path behind ``DeepSort.update`` of the reference's video demo (
 upload, ``Net(reid=True)`` (model.py:49-93) and a download of the 512-vector -- one box at a time.  Here the boxes of N frames are cut
 out of the frames where they lie on the device (csrc/reid_crops.hip, two launches), written straight into the input tensor of ONE
 ``Engine("reid", ...)`` plan and embedded in one graph replay.  The batch is static (`capacity` crops): a data-dependent batch would
-need the number of selected rows on the host, i.e. a synchronisation.  The tracker itself (Kalman filter, matching) stays with the
-caller: it is sequential host logic over a handful of boxes.
+need the number of selected rows on the host, i.e. a synchronisation.  The tracker that consumes the features is track.DeepSortTracker:
+its gallery and cost matrix stay on the device with them, its sequential logic (Kalman filter, matching) runs on the host.
 """
 import ctypes
 

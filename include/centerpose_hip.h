@@ -539,6 +539,40 @@ int cp_reid_crop_frames_host(const void* table_host, int N, const float* rows, i
 int cp_reid_crop_yuv_frames_host(const void* table_host, int N, const int* coef, const float* rows, int M, float vis_thresh,
                                  const int* slots, int cap, const void* norm, float* out);
 
+/* ---- track association: the DeepSort appearance gallery and its cost matrix on the device (track.DeepSortTracker) ----------------------
+ * What NearestNeighborDistanceMetric keeps and evaluates on the host (demo/tracking/sort/nn_matching.py:99-177): per track the last
+ * `budget` feature vectors and, per frame, the smallest cosine distance of every detection to them.  S independent streams, Tcap track
+ * slots per stream, q detection slots per stream; the state belongs to the caller and is passed as pointers:
+ *   gallery DEVICE float32 [S * Tcap, budget, 512]: a ring of the last `budget` features per track slot, stored as given (not normalised);
+ *   ginv    DEVICE float32 [S * Tcap, budget]: 1 / |row| of every ring row.
+ * cp_track_cost_f32: one launch.  glen: DEVICE int [S * Tcap], the valid ring rows per slot (capped at budget; 0 = skip this slot);
+ *   features DEVICE float32 [>= S * q, 512] and slots DEVICE int [>= S * q] as cp_reid_select_rows / the re-id plan leave them (slot
+ *   s * q + d belongs to stream s; slots holds n * M + m or -1); rows DEVICE float32 [S, M, 56].  out: DEVICE float32, cost[S, Tcap, q]
+ *   followed by det[S, q, 5]:
+ *     cost[s, t, d] = min over g < glen[s, t] of 1 - <G[s, t, g], F[s * q + d]> * ginv[s, t, g] * (1 / |F[s * q + d]|), float32 products on
+ *       the exact-f32 matrix cores; +inf where glen is 0 or the detection slot is unused (slots < 0 or >= S * M).  Ring rows >= glen are
+ *       not read.  A NaN distance (a zero vector) does not take part in the min.
+ *     det[s, d] = the first five floats (x1, y1, x2, y2, score) of row slots[s * q + d]; zeros for an unused slot.
+ * cp_track_append_f32: one launch, one block per entry of table DEVICE int [n, 3] = (feature slot, track slot, ring position), the slots
+ *   counted over all streams: the feature is copied into ring row (track slot, position) bit for bit and ginv gets 1.0f / sqrtf(float(sum
+ *   of squares)), the sum taken in double in one fixed order (csrc/track_host.h) so that the device and the host twin write the same bits.
+ *   An entry with a negative index or a position >= budget writes nothing.  The caller vouches that the indices lie inside its buffers and
+ *   that no two entries name the same ring row; ordered after the cost launch by the stream.  n = 0 succeeds and launches nothing.
+ *   Checked before anything is launched (rc 1, cp_last_error): budget in 1..128, Tcap in 1..1024, q >= 1, S in 1..65535, M >= 0, S * Tcap *
+ *   budget ring rows <= 2^31 - 1 (rows are counted in int; every float offset is size_t), S * q and S * M <= 2^24, n in 0..2^24, null
+ *   pointers, a gallery or feature pointer that is not 16-byte aligned.  cp_last_kernel(): track_cost_kernel, track_append_kernel.
+ * cp_track_cost_host / cp_track_append_host: HOST only -- sequential twins over host arrays, same checks.  The append twin is what the
+ *   kernel is pinned to bit for bit; the cost twin sums in float in k order and agrees with the kernel to rounding.
+ * cp_linear_assignment_host: HOST only -- rectangular minimum-cost assignment of cost[rows, cols] (float64, row stride ld, finite) by
+ *   shortest augmenting paths: min(rows, cols) pairs, row_to_col[r] = the column of row r or -1.  At most 4096 x 4096. */
+int cp_track_cost_f32(const float* gallery, const float* ginv, const int* glen, const float* features, const int* slots, const float* rows,
+                      int M, int S, int Tcap, int budget, int q, float* out, void* stream);
+int cp_track_append_f32(float* gallery, float* ginv, const float* features, const int* table, int n, int budget, void* stream);
+int cp_track_cost_host(const float* gallery, const float* ginv, const int* glen, const float* features, const int* slots, const float* rows,
+                       int M, int S, int Tcap, int budget, int q, float* out);
+int cp_track_append_host(float* gallery, float* ginv, const float* features, const int* table, int n, int budget);
+int cp_linear_assignment_host(const double* cost, int rows, int cols, int ld, int* row_to_col);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
