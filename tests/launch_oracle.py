@@ -262,6 +262,8 @@ def build_launches(case):
     u = None
     if row.kind == "wino":
         u = (ops.pack_wino24_weight if row.family == "wino24" else ops.pack_wino_weight)(wp, p["cin"], cp)
+    # split_bf16=False: these rows name the f32 kernels whatever CP_SPLIT_BF16 says; igemm_bf16x3_kernel has rows of its own
+    # (tests/bf16x3_oracle.py: all four instantiations forced, per element and with exact-answer cases)
     if S == 1:
         return [ops.conv2d_launch(srcs, wp, sc, sh, out, cout=cp, act=relu, res=res, wino=u, split_bf16=False, **kw)], read
     ld = cp if u is not None else wp.shape[0]                                      # the generic kernel stores whole N tiles of raw sums

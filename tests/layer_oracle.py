@@ -617,7 +617,7 @@ def _family(kinds):
 
 def run_plan(arch, B, H, W, seed=317, device="cuda"):
     """Build the plan of `arch` behind a RecordingBuilder and run it record by record.  -> dict(launches, checked, kernels (set of
-    device kernel names), worst {family: (ratio, text)}, failures [text])."""
+    device kernel names), worst {family: (ratio, text)}, failures [text], launch_list [`_launch_facts`])."""
     sd = checkpoint(arch, seed, H, W)
     dev = torch.device(device)
     images = synth.make_images(B, H, W).to(dev)
@@ -662,7 +662,19 @@ def run_plan(arch, B, H, W, seed=317, device="cuda"):
                     rep["worst"][fam] = (w.ratio, "%s [%s] at %s" % (label, ",".join(sorted(set(kn))), w.loc))
                 if fail:
                     rep["failures"].append("%s output %d [%s]: %s" % (label, j, ",".join(kn), fail))
+    rep["launch_list"] = [_launch_facts(name, launch) for _, name, _, launch in pb.launches]
     return rep
+
+
+def _launch_facts(name, launch):
+    """what a dispatch rule looks at, without holding the launch's buffers: dict(name, fn, kernel) and, for cp_conv2d_f32, the descriptor
+    fields and whether every source is 16-byte aligned"""
+    f = dict(name=name, fn=launch.fn, kernel=launch.kernel)
+    if launch.fn == "cp_conv2d_f32":
+        d = launch.desc
+        f.update({k: getattr(d, k) for k in ("tile", "inNCHW", "ldw", "nsrc", "kh", "kw", "Cout", "ksplit", "nsub")})
+        f.update(srcC0=d.srcC[0], aligned=all(t.data_ptr() % 16 == 0 for t in launch.tensors[:d.nsrc]))
+    return f
 
 
 def _device_outputs(pb, rec, ll):

@@ -6,7 +6,8 @@ The MFMA kernels do their address arithmetic in 32 bits and the lau
     pixels, the last block, the last tap -- no thread enumeration) together with the launchers' checks (`checks`, `accepts`), the word
     width being a parameter: at 16 bits the same arithmetic drives numpy emulations of the generic producer and of the DCN record
     (`emulate_generic`, `emulate_dcn`) that tests/test_limit_oracle_cpu.py mutates;
-(b) holds `ROWS`: one stand-alone launch per kernel family at LIM, the variant forced as in tests/launch_oracle.py;
+(b) holds `ROWS`: one stand-alone launch per kernel family at LIM, the variant forced as in tests/launch_oracle.py (the opt-in split-bf16
+    kernel with `split_bf16=True` and CP_SPLIT_BF16_TILE, as in tests/bf16x3_oracle.py);
 (c) judges a row twice (`run_row`): crops against the float64 reference with `layer_oracle`'s unchanged per-element bound (`judged_crops`),
     and image 2 (image 1) of the LIM launch bit for bit against the same forced variant run on that image ALONE, copied to a fresh buffer
     where every offset is small.
@@ -189,6 +190,15 @@ def audit(family, s, w=32, BM=64, BN=16, field=None):
     M = B * Ho * Wo
     q = []
     add = lambda name, where, ctype, lo_, hi: q.append(_q(name, where, ctype, lo_, hi, w))
+    if family == "bf16x3":                                                # igemm_bf16x3_kernel<BM, BN>: its own producer, the generic epilogue
+        mx = max(s["lds"])
+        add("a.M = B*Ho*Wo", "conv_igemm.hip:335", "int", M, M)
+        add("m = m0 + tid/QS + s*128", "conv_igemm_bf16x3.hip:161", "int", 0, (cdiv(M, BM) - 1) * BM + BM - 1)
+        add("ps.boff = b*H*W", "conv_igemm_bf16x3.hip:164", "int", -1, (B - 1) * H * W)
+        add("boff + iy*W + ix", "conv_igemm_bf16x3.hip:189", "int", 0, last)
+        # q*8 floats (half of a pixel's k-step, BM = 128: the second float4 is 16 bytes past aoff, added to the 64-bit pointer) or q*4 (quarter)
+        add("aoff", "conv_igemm_bf16x3.hip:189", "unsigned", 0, (last * mx + (12 if BM == 64 else 8)) * 4)
+        q.append(_grid_q("grid", "conv_igemm_bf16x3.hip:280", cdiv(M, BM) * (s["ldw"] // BN) * s["nsub"] * s["S"], w))
     if family in ("generic", "generic_stem", "group", "dcn", "pw"):
         add("a.M = B*Ho*Wo", "conv_igemm.hip:335", "int", M, M)
         add("m = m0 + row", "conv_igemm.hip:70", "int", 0, (cdiv(M, BM) - 1) * BM + BM - 1)
@@ -358,12 +368,15 @@ def _gather(mem, byte_off, ok):
     return np.where(ok, v, np.float32(0))
 
 
-def emulate_generic(x, wts, w=16, mutate=None):
+def emulate_generic(x, wts, w=16, mutate=None, slot=4):
     """the generic NHWC producer (conv_igemm.hip:70-113) of a 3x3 / stride 1 / pad 1 convolution at word width w: x [B, H, W, ld] float32
     (all ld channels are the source), wts [3, 3, ld] -> out [B, H, W] (one output channel, float64 sums of the gathered float32 values).
     aoff = ((unsigned)(boff + iy*W + ix) * ld + q*4) * 4 wraps at w bits and is ZERO-extended onto the 64-bit base.
     mutate: "signed" -- the offset register is an int, sign-extended; "narrow_base" -- the image's byte base b*H*W*ld*4 is formed in a w-bit
-    int of its own and added to a small in-image offset."""
+    int of its own and added to a small in-image offset.
+    slot: floats a staging thread owns -- 4: one float4 (the generic kernel; the split-bf16 kernel's quarter staging, BM = 64), 8: the
+    split-bf16 kernel's half staging (conv_igemm_bf16x3.hip:189, 196-197): aoff carries q*8 and the second float4 is 16 bytes further on,
+    added to the 64-bit pointer."""
     B, H, W, ld = x.shape
     mem = x.reshape(-1)
     b, oy, ox = np.meshgrid(np.arange(B), np.arange(H), np.arange(W), indexing="ij")
@@ -373,11 +386,11 @@ def emulate_generic(x, wts, w=16, mutate=None):
             iy, ix = oy - 1 + ky, ox - 1 + kx
             ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
             for c in range(ld):
-                qq, e = c // 4, c % 4
+                qq, e = c // slot, c % slot
                 if mutate == "narrow_base":
-                    off = wrap(b * H * W * ld * 4, "int", w) + wrap(((iy * W + ix) * ld + qq * 4) * 4, "unsigned", w)
+                    off = wrap(b * H * W * ld * 4, "int", w) + wrap(((iy * W + ix) * ld + qq * slot) * 4, "unsigned", w)
                 else:
-                    off = wrap(((b * H * W + iy * W + ix) * ld + qq * 4) * 4, "int" if mutate == "signed" else "unsigned", w)
+                    off = wrap(((b * H * W + iy * W + ix) * ld + qq * slot) * 4, "int" if mutate == "signed" else "unsigned", w)
                 out += wts[ky, kx, c] * _gather(mem, np.where(ok, off, 0) + 4 * e, ok).astype(np.float64)
     return out
 
@@ -443,6 +456,7 @@ def _r(id, kind, family, audit_, kernel, **p):
 
 
 IG, DCN = L.IG, L.DCN
+SB = "igemm_bf16x3_kernel<%d, %d>"
 # cin channels from channel c0 of the 64-wide buffer; th x tw: the kernel's tile in output pixels (GEMM kernels: 8 rows of M tiles)
 ROWS = [
     _r("ig-1x1", "conv", "direct", "generic", IG % "128, 32, 4, 1, 32, false", cin=32, c0=16, cout=20, k=1, pad=0, tile=128032, res=True),
@@ -464,6 +478,11 @@ ROWS = [
     # group launches: member 0 at LIM, member 1 small (B = 2, 19 x 37); the translation runs repeat the launch with image 2 / image 1 of member 0 alone
     _r("group-igemm", "group", "direct", "group", "igemm_conv_group_kernel", cin=16, c0=16, cout=40),
     _r("group-wino24", "group24", "wino24", "wino24", "conv3x3_wino24_group_kernel<true>", cin=32, c0=0, cout=24, th=16),
+    # the split-bf16 kernel (opt-in), forced with split_bf16=True and CP_SPLIT_BF16_TILE = `sb`: half staging (BM = 128) and quarter staging
+    # (BM = 64).  res_host: source + output + residual at 48 physical channels leave no room under MEM_LIMIT for a stand-alone image beside
+    # them, so the residual of the translated images waits on the host while those run
+    _r("sb-3x3-s1", "conv", "direct", "bf16x3", SB % (128, 64), cin=16, c0=48, cout=40, sb="128x64"),
+    _r("sb-1x1", "conv", "direct", "bf16x3", SB % (64, 64), cin=32, c0=16, cout=40, k=1, pad=0, sb="64x64", res=True, res_host=True),
 ]
 ROW = {r.id: r for r in ROWS}
 assert len(ROW) == len(ROWS)
@@ -500,8 +519,8 @@ def _ldw(cout):
 
 def row_tile(row):
     """(BM, BN) of the row's GEMM instantiation, from its kernel name"""
-    if "<" in row.kernel and row.kernel.split("<")[0] in ("igemm_conv_kernel", "dcn_igemm_kernel"):
-        a = row.kernel.split("<")[1].split(",")
+    if "<" in row.kernel and row.kernel.split("<")[0] in ("igemm_conv_kernel", "dcn_igemm_kernel", "igemm_bf16x3_kernel"):
+        a = row.kernel.rstrip(">").split("<")[1].split(",")
         return int(a[0]), int(a[1])
     return (64, 64)
 
@@ -603,6 +622,7 @@ class Built:
         from centerpose_amd import ops
         p = row.p
         self.row, self.sd = row, sd
+        self.res_host = None                                               # {image: CPU residual}, once `run_row` has let the device buffer go
         B = p["B"] if parent is None else 1
         H, W, co = p["H"], p["W"], p["cout"]
         k = 3 if row.kind in ("group", "group24", "head", "dcn", "wino") else p["k"]
@@ -620,8 +640,8 @@ class Built:
         else:                                                              # the image ALONE, in fresh buffers: every offset is small
             self.src = parent.src[image:image + 1].clone()
             self.res = None
-            if parent.res is not None:
-                rb = parent.res[image:image + 1]
+            if parent.res is not None or parent.res_host:
+                rb = parent.res_host[image] if parent.res is None else parent.res[image:image + 1]
                 self.res = torch.zeros(1, Ho, Wo, cp + 4, device="cuda")[..., :cp]
                 self.res.copy_(rb)
             self.om = None
@@ -670,6 +690,9 @@ class Built:
         sc, sh = ops.fold_bn(co, bnp)
         srcs = [self.src[..., a:a + n] for a, n in p["cat"]] if p.get("cat") else [x]
         kw = dict(kh=k, kw=k, stride=st, pad=pad, tile=p["tile"])
+        if p.get("sb"):
+            self.launches = [_forced_sb(p["sb"], lambda: ops.conv2d_launch(srcs, wp, sc, sh, out, cout=cp, act=relu, res=self.res, split_bf16=True, **kw))]
+            return
         u = None
         if row.kind == "wino":
             u = (ops.pack_wino24_weight if row.family == "wino24" else ops.pack_wino_weight)(wp, p["cin"], cp)
@@ -715,6 +738,20 @@ class Built:
     def out_nhwc(self):
         """the physical output as [B, Ho, Wo, c] (heads: a permuted view of the NCHW map)"""
         return self.out.view.permute(0, 2, 3, 1) if self.out.nchw else self.out.view
+
+
+def _forced_sb(tile, make):
+    """make() with CP_SPLIT_BF16_TILE = tile: ops.split_bf16_tile reads the switch when the launch is BUILT"""
+    import os
+    saved = os.environ.get("CP_SPLIT_BF16_TILE")
+    os.environ["CP_SPLIT_BF16_TILE"] = tile
+    try:
+        return make()
+    finally:
+        if saved is None:
+            del os.environ["CP_SPLIT_BF16_TILE"]
+        else:
+            os.environ["CP_SPLIT_BF16_TILE"] = saved
 
 
 def _group_launch(ops, kind, members):
@@ -830,6 +867,9 @@ def run_row(rid):
             fails += _judge_small(big)
         # translation: the image alone, bit for bit
         big.launches = None                                                    # a split-K workspace goes before the stand-alone launches
+        if p.get("res_host"):
+            big.res_host = {img: big.res[img:img + 1].cpu() for img in p["images"]}
+            big.res = None                                                     # the device copy goes; Built takes the image from the host
         torch.cuda.empty_cache()
         for img in p["images"]:
             one = Built(row, sd, parent=big, image=img)

@@ -119,6 +119,8 @@ def test_head_points_plane_index_overflowed_at_an_accepted_shape():
 # check of the same path always refuses first.
 VERDICTS = {
     "conv bytes": "slack: one pixel (the last pixel's float4 ends 192 bytes below the limit when the count is refused)",
+    "conv bytes (igemm_bf16x3_kernel)": "slack: one pixel, as above (largest aoff at the refused count 2^32 - 208 with quarter, 2^32 - 224 with half staging; "
+                                        "tests/test_bf16x3_oracle_cpu.py::test_verdict_for_the_split_kernel)",
     "conv pixels": "dead: behind conv bytes (NHWC, ld >= 16: 2^26 pixels) and behind conv nchw floats (C >= 1)",
     "conv rows": "slack: 255 rows (a.M itself first overflows at 2^31; the last 256-row block's index stays below it until then)",
     "conv nchw floats": "slack: one image plane (boff = (B - 1) C H W); the stem kernels' s_g needs less",

@@ -29,6 +29,7 @@ MUST_COVER = (
     "igemm_conv_kernel<", "splitk_reduce_kernel", "pw_conv_kernel<", "conv3x3_patch_kernel<", "conv3x3_c16_kernel<1, 1", "conv3x3_c16_kernel<2, 2",
     "conv3x3_wino_kernel<", "conv3x3_wino_vs64_kernel<0, 0>", "conv3x3_wino24_kernel<", "conv3x3_wino_vs64_kernel<2, 0>", "head_wino24_kernel<1, 0>",
     "dcn_igemm_kernel<64, 32", "dcn_igemm_kernel<128, 32", "igemm_conv_group_kernel", "conv3x3_wino24_group_kernel<",
+    "igemm_bf16x3_kernel<128, 64>", "igemm_bf16x3_kernel<64, 64>",        # the opt-in split-bf16 kernel: half and quarter staging
 )
 _reports = {}
 
