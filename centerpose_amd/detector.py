@@ -33,6 +33,10 @@ import torch
 
 from . import _lib
 from .decode import multi_pose_decode
+# frames.py and draw.py hold what used to be defined here: besides what this module uses, the names callers import from it stay
+from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv      # noqa: F401
+from .frames import (FRAME_DESC, PRE_DESC, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO, _check_layout, byte_range,      # noqa: F401
+                     check_rows, frame_geometry, frame_writable, identity_table, yuv_frame_geometry)
 from .model import create_model, load_model
 from .post_process import get_affine_transform
 
@@ -100,238 +104,6 @@ def _imread(path):
             return np.load(path)
         raise RuntimeError("cv2 is not available here: pass an HxWx3 uint8 numpy array (or a .npy path) to run()")
     return cv2.imread(path)
-
-
-# cp_pre_desc (include/centerpose_hip.h): one source image of a batched pre-process
-PRE_DESC = np.dtype([("src_off", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"),
-                     ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
-
-
-# cp_frame_desc (include/centerpose_hip.h): one source frame on the device, addressed by pointer and strides
-FRAME_DESC = np.dtype([("base", "<u8"), ("row_stride", "<i8"), ("pix_stride", "<i8"), ("ch_off", "<i8", (3,)), ("mid_off", "<i8"),
-                       ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"), ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
-
-# cp_yuv_frame_desc (include/centerpose_hip.h): one source frame on the device in 4:2:0 YUV planes
-YUV_FRAME_DESC = np.dtype([("y_base", "<u8"), ("y_row", "<i8"), ("y_pix", "<i8"), ("u_base", "<u8"), ("v_base", "<u8"), ("c_row", "<i8"),
-                           ("c_pix", "<i8"), ("mid_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("NH", "<i4"), ("NW", "<i4"),
-                           ("mi", "<f8", (6,)), ("slot", "<i4"), ("pad", "<i4")])
-
-LAYOUTS, COLORS, YUV_COLORS = ("hwc", "chw"), ("bgr", "rgb"), ("nv12", "nv21", "i420")
-
-# limited-range YUV -> BGR matrices (csrc/yuv_arith.h): (CY, CVR, CVG, CUG, CUB, YOFF), every entry round(k * 2^20)
-YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026, 16),       # 1.164, 1.596, -0.813, -0.391, 2.018
-                "bt709": (1220542, 1880097, -558891, -223347, 2214593, 16)}       # 1.164, 1.793, -0.533, -0.213, 2.112
-
-
-def _check_layout(layout, color, matrix="bt601"):
-    if layout not in LAYOUTS:
-        raise _lib.CenterposeHipError("unknown layout %r: one of %s" % (layout, ", ".join(LAYOUTS)))
-    if color not in COLORS + YUV_COLORS:
-        raise _lib.CenterposeHipError("unknown color %r: one of %s" % (color, ", ".join(COLORS + YUV_COLORS)))
-    if matrix not in YUV_MATRICES:
-        raise _lib.CenterposeHipError("unknown matrix %r: one of %s" % (matrix, ", ".join(sorted(YUV_MATRICES))))
-    if color in YUV_COLORS and layout != "hwc":
-        raise _lib.CenterposeHipError("layout=%r does not apply to color=%r: YUV frames are given as planes" % (layout, color))
-    if color not in YUV_COLORS and matrix != "bt601":
-        raise _lib.CenterposeHipError("matrix=%r applies to YUV frames (color %s) only, not to color=%r" % (matrix, " / ".join(YUV_COLORS), color))
-
-
-def frame_geometry(shape, strides, layout="hwc", color="bgr"):
-    """How a uint8 frame of the given shape and strides (in elements == bytes) is addressed: (H, W, row_stride, pix_stride, ch_off),
-    channel k of the network (cv2's B, G, R) of pixel (y, x) at byte y * row_stride + x * pix_stride + ch_off[k] from the frame's first
-    element.  layout "hwc": [H,W,C], "chw": [C,H,W]; C = 3 or 4 (a fourth channel is never read); color: the order of the first three
-    channels in memory.  A pure function of its arguments: nothing is copied, any strides (crops, padded rows, expanded views) go."""
-    _check_layout(layout, color)
-    if color in YUV_COLORS:
-        raise _lib.CenterposeHipError("color=%r frames are planes: yuv_frame_geometry" % color)
-    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
-    if len(shape) != 3 or len(strides) != 3:
-        raise _lib.CenterposeHipError("a frame is 3-D ([H,W,C] or [C,H,W]), got shape %s" % (shape,))
-    (H, W, C), (sh, sw, sc) = (shape, strides) if layout == "hwc" else ((shape[1], shape[2], shape[0]), (strides[1], strides[2], strides[0]))
-    if C not in (3, 4):
-        raise _lib.CenterposeHipError("a frame has 3 or 4 channels (layout %r of shape %s has %d)" % (layout, shape, C))
-    if H <= 0 or W <= 0:
-        raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shape,))
-    if min(sh, sw, sc) < 0:
-        raise _lib.CenterposeHipError("negative strides %s are not addressable" % (strides,))
-    return H, W, sh, sw, ((0, sc, 2 * sc) if color == "bgr" else (2 * sc, sc, 0))
-
-
-def yuv_frame_geometry(shapes, strides, color="nv12", dtypes=None):
-    """How a 4:2:0 YUV frame given as uint8 planes is addressed.  shapes / strides (in elements == bytes): one entry per tensor of the
-    frame -- (y [H,W], uv [ceil(H/2),ceil(W/2),2]) for "nv12" / "nv21", (y, u, v) with u, v [ceil(H/2),ceil(W/2)] of equal strides for
-    "i420", or ONE 2-D surface [H*3/2, W] (H, W even, any row stride: the decoder's layout, chroma rows below the luma rows) for
-    "nv12" / "nv21"; dtypes: the tensors' dtypes when known (anything but uint8 raises).
-    -> (H, W, y_row, y_pix, u_off, v_off, c_row, c_pix): Y(r, c) at byte r * y_row + c * y_pix of the first tensor, U(r, c) at byte
-    u_off + (r >> 1) * c_row + (c >> 1) * c_pix of the tensor that holds it, V(r, c) the same from v_off (the surface itself, the uv
-    plane, or the u and the v plane, each from its own first element).  A pure function of its arguments: nothing is copied, any
-    non-negative strides (pitched rows, crops at even origins, expanded planes) go."""
-    _check_layout("hwc", color)
-    if color not in YUV_COLORS:
-        raise _lib.CenterposeHipError("color=%r frames are not planes: frame_geometry" % color)
-    shapes = [tuple(int(v) for v in s) for s in shapes]
-    strides = [tuple(int(v) for v in s) for s in strides]
-    if len(shapes) != len(strides) or any(len(a) != len(b) for a, b in zip(shapes, strides)):
-        raise _lib.CenterposeHipError("one stride per dimension of every plane: shapes %s, strides %s" % (shapes, strides))
-    for dt in (dtypes or ()):
-        if dt is not torch.uint8 and (isinstance(dt, torch.dtype) or np.dtype(dt) != np.uint8):
-            raise _lib.CenterposeHipError("the planes of a YUV frame must be uint8 (got %s)" % (dt,))
-    if any(v < 0 for s in strides for v in s):
-        raise _lib.CenterposeHipError("negative strides %s are not addressable" % (strides,))
-    if len(shapes) == 1:                                       # the decoder's surface: luma rows, then the interleaved chroma rows
-        if color == "i420":
-            raise _lib.CenterposeHipError("an i420 frame is three planes (y, u, v); one surface tensor is nv12 / nv21")
-        if len(shapes[0]) != 2:
-            raise _lib.CenterposeHipError("a %s surface is one 2-D tensor [H*3/2, W], got shape %s" % (color, shapes[0]))
-        (rows, W), (pitch, pix) = shapes[0], strides[0]
-        H = rows * 2 // 3
-        if rows <= 0 or W <= 0:
-            raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shapes[0],))
-        if rows % 3 or H % 2 or W % 2:
-            raise _lib.CenterposeHipError("a %s surface [H*3/2, W] needs even H and W, got shape %s: pass the planes (y, uv) otherwise"
-                                          % (color, shapes[0]))
-        first = H * pitch                                      # t[H:].unflatten(1, (W // 2, 2)): strides (pitch, 2 * pix, pix)
-        u_off, v_off = (first, first + pix) if color == "nv12" else (first + pix, first)
-        return H, W, pitch, pix, u_off, v_off, pitch, 2 * pix
-    want = 2 if color in ("nv12", "nv21") else 3
-    if len(shapes) != want:
-        raise _lib.CenterposeHipError("a %s frame is %s, got %d tensors" % (color, "(y, uv) or one surface" if want == 2 else "(y, u, v)",
-                                                                          len(shapes)))
-    if len(shapes[0]) != 2:
-        raise _lib.CenterposeHipError("the y plane is 2-D [H,W], got shape %s" % (shapes[0],))
-    H, W = shapes[0]
-    if H <= 0 or W <= 0:
-        raise _lib.CenterposeHipError("a frame of shape %s has no pixels" % (shapes[0],))
-    ch, cw = (H + 1) // 2, (W + 1) // 2
-    if want == 2:
-        if shapes[1] != (ch, cw, 2):
-            raise _lib.CenterposeHipError("the uv plane of a %d x %d %s frame is [%d,%d,2], got shape %s" % (H, W, color, ch, cw, shapes[1]))
-        c_row, c_pix, sc = strides[1]
-        u_off, v_off = (0, sc) if color == "nv12" else (sc, 0)
-    else:
-        if shapes[1] != (ch, cw) or shapes[2] != (ch, cw):
-            raise _lib.CenterposeHipError("the u and v planes of a %d x %d i420 frame are [%d,%d], got shapes %s and %s"
-                                          % (H, W, ch, cw, shapes[1], shapes[2]))
-        if strides[1] != strides[2]:
-            raise _lib.CenterposeHipError("the u and v planes must have equal strides (%s and %s)" % (strides[1], strides[2]))
-        (c_row, c_pix), u_off, v_off = strides[1], 0, 0
-    return H, W, strides[0][0], strides[0][1], u_off, v_off, c_row, c_pix
-
-
-def frame_writable(shape, strides):
-    """Whether a view of the given shape and strides (in elements == bytes) may be WRITTEN: no two of its indices address the same
-    byte.  The dimensions with more than one index, sorted by stride: each stride must be at least the extent (last addressed offset
-    + 1) of the dimensions below it.  Sufficient, not necessary: crops, padded rows, planar and permuted views pass; expanded (stride
-    0) and overlapping (as_strided windows) views and negative strides do not.  A pure function of its arguments."""
-    dims = sorted((int(st), int(n)) for n, st in zip(shape, strides) if int(n) > 1)
-    if any(int(n) <= 0 for n in shape):
-        return False
-    extent = 1
-    for st, n in dims:
-        if st < extent:
-            return False
-        extent += (n - 1) * st
-    return True
-
-
-def byte_range(address, shape, strides):
-    """[first, last + 1) of the bytes a uint8 view with non-negative strides addresses from `address`."""
-    return int(address), int(address) + sum((int(n) - 1) * int(st) for n, st in zip(shape, strides)) + 1
-
-
-# cp_draw_style (include/centerpose_hip.h)
-DRAW_STYLE = np.dtype([("box_thickness", "<i4"), ("limb_radius", "<i4"), ("joint_radius", "<i4"), ("palette", "u1", (36, 4))])
-
-# the limbs of a pose in paint order, as joint pairs (COCO keypoint order: 0 nose, odd = left, even = right)
-DRAW_LIMBS = ((0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6), (5, 6), (5, 7), (7, 9), (6, 8), (8, 10), (5, 11), (6, 12), (11, 12), (11, 13),
-              (13, 15), (12, 14), (14, 16))
-# this project's palette, (B, G, R): one colour for left-side parts, one for right-side parts, one for mid-line parts and the box
-DRAW_LEFT, DRAW_RIGHT, DRAW_MID = (0, 140, 255), (255, 160, 0), (60, 220, 60)
-
-
-def _side_color(joints):
-    sides = {j % 2 for j in joints if j > 0}                   # the nose is on the mid-line
-    return DRAW_MID if len(sides) != 1 else (DRAW_LEFT if sides == {1} else DRAW_RIGHT)
-
-
-class DrawStyle:
-    """How draw_results paints: box_thickness 0..64 (0: no box), limb_radius -1 (no limbs) or 1..64, joint_radius -1 (no joints) or
-    0..64, and the colours as (B, G, R): one for the box, one per limb (DRAW_LIMBS order), one per joint.  Defaults: thickness 2, limb
-    radius 1, joint radius 2; a limb or joint on the left side DRAW_LEFT, on the right side DRAW_RIGHT, the box, the nose and the limbs
-    that join the two sides DRAW_MID."""
-
-    def __init__(self, box_thickness=2, limb_radius=1, joint_radius=2, box_color=None, limb_colors=None, joint_colors=None):
-        self.box_thickness, self.limb_radius, self.joint_radius = int(box_thickness), int(limb_radius), int(joint_radius)
-        self.box_color = tuple(box_color) if box_color is not None else DRAW_MID
-        self.limb_colors = [tuple(c) for c in limb_colors] if limb_colors is not None else [_side_color(ab) for ab in DRAW_LIMBS]
-        self.joint_colors = [tuple(c) for c in joint_colors] if joint_colors is not None else [_side_color((j,)) for j in range(17)]
-        if not (0 <= self.box_thickness <= 64):
-            raise _lib.CenterposeHipError("box_thickness %d outside 0..64" % self.box_thickness)
-        if not (self.limb_radius == -1 or 1 <= self.limb_radius <= 64):
-            raise _lib.CenterposeHipError("limb_radius %d is neither -1 nor in 1..64 (radius 0 would dot the lines)" % self.limb_radius)
-        if not (-1 <= self.joint_radius <= 64):
-            raise _lib.CenterposeHipError("joint_radius %d outside -1..64" % self.joint_radius)
-        if len(self.limb_colors) != 18 or len(self.joint_colors) != 17:
-            raise _lib.CenterposeHipError("a style has 18 limb colours and 17 joint colours")
-        for c in self.palette():
-            if len(c) != 3 or any(not (0 <= int(v) <= 255) for v in c):
-                raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
-
-    def palette(self):
-        """The 36 (B, G, R) colours in paint order: the box, the limbs, the joints."""
-        return [self.box_color] + list(self.limb_colors) + list(self.joint_colors)
-
-    def struct(self, matrix=None):
-        """One DRAW_STYLE record; `matrix` ("bt601" / "bt709"): the palette as (Y, U, V) for YUV frames."""
-        rec = np.zeros(1, DRAW_STYLE)
-        rec["box_thickness"], rec["limb_radius"], rec["joint_radius"] = self.box_thickness, self.limb_radius, self.joint_radius
-        pal = self.palette() if matrix is None else palette_to_yuv(self.palette(), matrix)
-        rec["palette"][0, :, :3] = np.asarray(pal, np.uint8)
-        return rec
-
-
-# limited-range BGR -> (Y, U, V) rows of (R, G, B) weights, 8 fractional bits
-YUV_FORWARD = {"bt601": ((66, 129, 25), (-38, -74, 112), (112, -94, -18)),
-               "bt709": ((47, 157, 16), (-26, -87, 112), (112, -102, -10))}
-
-
-def palette_to_yuv(colors, matrix="bt601"):
-    """(B, G, R) colours -> (Y, U, V) by the usual limited-range 8-bit forms, e.g. bt601 Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16,
-    U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128, V = ((112 R - 94 G - 18 B + 128) >> 8) + 128 (arithmetic shifts).  This is NOT
-    the inverse of csrc/yuv_arith.h's YUV -> BGR: a painted colour read back through the pre-process differs by a few levels."""
-    if matrix not in YUV_FORWARD:
-        raise _lib.CenterposeHipError("unknown matrix %r: one of %s" % (matrix, ", ".join(sorted(YUV_FORWARD))))
-    ky, ku, kv = YUV_FORWARD[matrix]
-    out = []
-    for b, g, r in colors:
-        b, g, r = int(b), int(g), int(r)
-        out.append((((ky[0] * r + ky[1] * g + ky[2] * b + 128) >> 8) + 16, ((ku[0] * r + ku[1] * g + ku[2] * b + 128) >> 8) + 128,
-                    ((kv[0] * r + kv[1] * g + kv[2] * b + 128) >> 8) + 128))
-    return out
-
-
-class _Staging:
-    """A pinned host buffer that grows on demand, and ONE stream-ordered upload of its first bytes per use.  `host()` waits for the
-    previous upload to have left the buffer before handing it out again (an event on that copy alone, not a device synchronisation)."""
-
-    def __init__(self):
-        self.buf = None
-        self.event = None
-
-    def host(self, nbytes):
-        if self.event is not None:
-            self.event.synchronize()
-            self.event = None
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, pin_memory=True)
-        return self.buf.numpy()[:nbytes]
-
-    def upload(self, nbytes):
-        dev = torch.empty(int(nbytes), dtype=torch.uint8, device="cuda")
-        dev.copy_(self.buf[:nbytes], non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record()
-        return dev
 
 
 def invert_warp(M):
@@ -405,16 +177,13 @@ class BaseDetector(object):
         color "nv12" / "nv21" / "i420": image is one 4:2:0 YUV frame on the device (a tuple of plane tensors or, for nv12 / nv21, one
         surface tensor), converted with `matrix` ("bt601" / "bt709") -- see pre_process_batch."""
         _check_layout(layout, color, matrix)
-        if color in YUV_COLORS:
-            x, metas = self.pre_process_batch([image], scale, layout, color, matrix)
-            return x, metas[0]
-        if isinstance(image, torch.Tensor):
-            if image.dim() != 3:
+        if color in YUV_COLORS or isinstance(image, torch.Tensor):
+            if color not in YUV_COLORS and image.dim() != 3:
                 raise _lib.CenterposeHipError("pre_process takes one 3-D frame tensor, got shape %s (N frames: pre_process_batch)"
                                               % (tuple(image.shape),))
-            x, metas = self.pre_process_batch([image], scale, layout, color)
+            x, metas = self.pre_process_batch([image], scale, layout, color, matrix)      # (bt601, checked above, unless YUV)
             return x, metas[0]
-        self._host_layout_only(layout, color)
+        FrameIO.host_layout_only(layout, color)
         if not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3):
             raise _lib.CenterposeHipError("pre_process expects an HxWx3 uint8 array (cv2.imread layout); there is no host fallback")
         height, width = image.shape[0:2]
@@ -448,101 +217,17 @@ class BaseDetector(object):
         raise NotImplementedError
 
     # -- N images at once ------------------------------------------------------------------------------------------------
-    def _staging(self, which):
-        st = self.__dict__.setdefault("_staging_buffers", {})
-        if which not in st:
-            st[which] = _Staging()
-        return st[which]
-
-    @staticmethod
-    def _check_batch(images):
-        images = list(images)
-        for im in images:
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.shape[0] > 0
-                    and im.shape[1] > 0):
-                raise _lib.CenterposeHipError("run_batch / pre_process_batch expect HxWx3 uint8 arrays (cv2.imread layout); there is no host fallback")
-        return images
-
-    @staticmethod
-    def _host_layout_only(layout, color, matrix="bt601"):
-        _check_layout(layout, color, matrix)      # unknown names raise
-        if (layout, color) != ("hwc", "bgr"):
-            raise _lib.CenterposeHipError("host arrays are taken in cv2's layout (HxWx3, BGR): layout=%r / color=%r apply to frames "
-                                          "on the device (CUDA uint8 tensors) only" % (layout, color))
-
     def _model_device(self):
         """The card the model's plans live on, with its index ("cuda" alone means the current device, as everywhere here)."""
         device = torch.device(self.model.device)
         return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
 
-    def _frame(self, t, layout, color):
-        """One device frame -> (address of pixel (0,0), H, W, row_stride, pix_stride, ch_off), all from the tensor's own shape,
-        strides and data pointer: a valid view cannot address outside its storage.  The tensor is never copied or made contiguous."""
-        if not t.is_cuda:
-            raise _lib.CenterposeHipError("a frame tensor on %s: frames given as tensors must be on the model's GPU (host frames are "
-                                          "passed as numpy arrays); there is no host fallback" % t.device)
-        if t.dtype != torch.uint8:
-            raise _lib.CenterposeHipError("a frame tensor must be uint8 (got %s)" % t.dtype)
-        geometry = frame_geometry(t.shape, t.stride(), layout, color)
-        device = self._model_device()
-        if t.device != device:
-            raise _lib.CenterposeHipError("a frame tensor on %s, the model is on %s" % (t.device, device))
-        return (t.data_ptr(),) + geometry
-
-    def _yuv_frame(self, frame, color):
-        """One device frame in 4:2:0 YUV -> (address of Y(0,0), H, W, y_row, y_pix, address of U(0,0), address of V(0,0), c_row, c_pix),
-        all from the plane tensors' own shapes, strides and data pointers.  One 2-D surface tensor (nv12 / nv21) is split into the views
-        t[:H] and t[H:].unflatten(1, (W // 2, 2)) by address alone.  Nothing is copied or made contiguous."""
-        planes = [frame] if isinstance(frame, (torch.Tensor, np.ndarray)) else list(frame)
-        if not planes:
-            raise _lib.CenterposeHipError("a %s frame without planes" % color)
-        if any(isinstance(t, np.ndarray) for t in planes):
-            if all(isinstance(t, np.ndarray) for t in planes):
-                raise _lib.CenterposeHipError("host arrays are taken in cv2's layout (HxWx3, BGR): color=%r applies to frames on the "
-                                              "device (CUDA uint8 plane tensors) only" % color)
-            raise _lib.CenterposeHipError("host arrays and device tensors mixed in one frame: pass all planes as CUDA tensors")
-        if not all(isinstance(t, torch.Tensor) for t in planes):
-            raise _lib.CenterposeHipError("a %s frame is a tuple of CUDA uint8 plane tensors (or one surface tensor for nv12 / nv21)" % color)
-        for t in planes:
-            if not t.is_cuda:
-                raise _lib.CenterposeHipError("a plane tensor on %s: the planes of a frame must be on the model's GPU; there is no host "
-                                              "fallback" % t.device)
-        H, W, y_row, y_pix, u_off, v_off, c_row, c_pix = yuv_frame_geometry([t.shape for t in planes], [t.stride() for t in planes], color,
-                                                                            [t.dtype for t in planes])
-        device = self._model_device()
-        for t in planes:
-            if t.device != device:
-                raise _lib.CenterposeHipError("a plane tensor on %s, the model is on %s" % (t.device, device))
-        u_plane, v_plane = (planes[0], planes[0]) if len(planes) == 1 else (planes[1], planes[-1])
-        return (planes[0].data_ptr(), H, W, y_row, y_pix, u_plane.data_ptr() + u_off, v_plane.data_ptr() + v_off, c_row, c_pix)
-
-    def _batch_input(self, images, layout, color, matrix="bt601"):
-        """What a batched call was given -> (images as a list, frames): frames is None for host arrays (the staging path), else one
-        `_frame` per device tensor (`_yuv_frame` per frame with a YUV color).  One 4-D tensor means N frames ([N,H,W,C] or [N,C,H,W])."""
-        _check_layout(layout, color, matrix)      # unknown names raise, whatever the input
-        if color in YUV_COLORS:
-            if isinstance(images, (torch.Tensor, np.ndarray)):
-                raise _lib.CenterposeHipError("a batch of %s frames is a list of frames (plane tuples or surface tensors), got one %s of "
-                                              "shape %s" % (color, type(images).__name__, tuple(images.shape)))
-            images = list(images)
-            host = sum(isinstance(im, np.ndarray) for im in images)
-            if 0 < host < len(images):
-                raise _lib.CenterposeHipError("host arrays and device tensors mixed in one call: pass all frames one way")
-            return images, [self._yuv_frame(im, color) for im in images]
-        if isinstance(images, torch.Tensor):
-            if images.dim() != 4:
-                raise _lib.CenterposeHipError("one tensor for N frames is 4-D ([N,H,W,C] or [N,C,H,W]), got shape %s; pass a list of "
-                                              "3-D frames otherwise" % (tuple(images.shape),))
-            images = images.unbind(0)
-        images = list(images)
-        tensors = sum(isinstance(im, torch.Tensor) for im in images)
-        if tensors == 0:
-            if images:
-                self._host_layout_only(layout, color)
-            return self._check_batch(images), None
-        if tensors != len(images):
-            raise _lib.CenterposeHipError("host arrays and device tensors mixed in one call: pass all frames one way")
-        return images, [self._frame(t, layout, color) for t in images]
+    @property
+    def _io(self):
+        """This detector's FrameIO, made on first use; it asks `_model_device` per call.  A `_staging_buffers` dict set before stands in."""
+        if "_frame_io" not in self.__dict__:
+            self._frame_io = FrameIO(lambda: self._model_device(), self.__dict__.get("_staging_buffers"))
+        return self._frame_io
 
     @staticmethod
     def _batch_layout(shapes):
@@ -565,11 +250,11 @@ class BaseDetector(object):
     def _pre_table(self, shapes, offsets, idx, scale, frames=None, yuv=False):
         """The descriptor table of one batched pre-process: images `idx` at `scale`, which must share one network input shape
         -> (table, scratch_bytes, inp_h, inp_w, metas).  Geometry, matrix and meta per image are pre_process's.  PRE_DESC rows with the
-        images' staging `offsets`, or, with `frames` (`_frame` per image), FRAME_DESC rows that address the frames where they lie
-        (`yuv`: `_yuv_frame` per image, YUV_FRAME_DESC rows)."""
+        images' staging `offsets`, or, with `frames` (a frames.Frame per image), FRAME_DESC rows that address the frames where they lie
+        (`yuv`: a frames.YuvFrame per image, YUV_FRAME_DESC rows): the identity table of these frames with the geometry filled in."""
         nb = 2 if self.cfg.TEST.FLIP_TEST else 1
         down = self.cfg.MODEL.DOWN_RATIO
-        table = np.zeros(len(idx), PRE_DESC if frames is None else (YUV_FRAME_DESC if yuv else FRAME_DESC))
+        table = np.zeros(len(idx), PRE_DESC) if frames is None else identity_table([frames[i] for i in idx], yuv)
         metas, scratch, inp = [], 0, None
         for j, i in enumerate(idx):
             height, width = shapes[i]
@@ -585,10 +270,6 @@ class BaseDetector(object):
             d["H"], d["W"], d["NH"], d["NW"], d["slot"] = height, width, new_h, new_w, nb * j
             if frames is None:
                 d["src_off"] = offsets[i]
-            elif yuv:
-                d["y_base"], _, _, d["y_row"], d["y_pix"], d["u_base"], d["v_base"], d["c_row"], d["c_pix"] = frames[i]
-            else:
-                d["base"], _, _, d["row_stride"], d["pix_stride"], d["ch_off"] = frames[i]
             if (new_h, new_w) != (height, width):
                 d["mid_off"] = scratch
                 scratch += new_h * new_w * 3
@@ -603,28 +284,6 @@ class BaseDetector(object):
         """float64 [N,6]: post_process's feature-map -> image matrix per image."""
         return np.stack([np.ascontiguousarray(get_affine_transform(m["c"], m["s"], 0, (m["out_width"], m["out_height"]), inv=1),
                                               np.float64).reshape(6) for m in metas])
-
-    def _upload_images(self, images, offsets, nbytes):
-        """The N images into the pinned staging buffer, ONE host-to-device copy -> device uint8 [nbytes]."""
-        st = self._staging("images")
-        host = st.host(nbytes)
-        for im, off in zip(images, offsets):
-            host[off:off + im.size] = im.reshape(-1)
-        return st.upload(nbytes)
-
-    def _upload_table(self, parts):
-        """Host arrays (descriptor tables, affines; 8-byte items) back to back in the pinned table buffer, ONE copy -> the device
-        uint8 views of the parts."""
-        raw = [np.ascontiguousarray(p).view(np.uint8).reshape(-1) for p in parts]
-        st = self._staging("table")
-        host = st.host(sum(r.size for r in raw))
-        pos, spans = 0, []
-        for r in raw:
-            host[pos:pos + r.size] = r
-            spans.append((pos, r.size))
-            pos += r.size
-        dev = st.upload(pos)
-        return [dev[a:a + n] for a, n in spans]
 
     def _launch_pre(self, staging, table_dev, table, scratch_bytes, inp_h, inp_w):
         """cp_preprocess_batch_u8_f32 for one table -> float32 [nb * N, 3, inp_h, inp_w] on the device."""
@@ -651,18 +310,13 @@ class BaseDetector(object):
         """cp_preprocess_frames_u8_f32 for one FRAME_DESC table -> float32 [nb * N, 3, inp_h, inp_w] on the device.  With `coef` (six
         ints, YUV_MATRICES): cp_preprocess_yuv_frames_u8_f32 for one YUV_FRAME_DESC table."""
         nb, n, x, scratch, mean, std, table = self._pre_buffers(table, scratch_bytes, inp_h, inp_w)
-        if coef is not None:
-            rc = _lib.lib().cp_preprocess_yuv_frames_u8_f32(
-                ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, (ctypes.c_int * 6)(*coef),
-                ctypes.c_void_p(scratch.data_ptr()), ctypes.c_size_t(scratch_bytes), _lib.ptr(x), nb * n, inp_h, inp_w,
-                mean.ctypes.data_as(ctypes.c_void_p), std.ctypes.data_as(ctypes.c_void_p), 1 if nb == 2 else 0, _lib.stream())
-            _lib.check(rc, "cp_preprocess_yuv_frames_u8_f32")
-            return x
-        rc = _lib.lib().cp_preprocess_frames_u8_f32(
-            ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n, ctypes.c_void_p(scratch.data_ptr()),
+        name = "cp_preprocess_frames_u8_f32" if coef is None else "cp_preprocess_yuv_frames_u8_f32"      # the same arguments but for `coef`
+        tables = (ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), n)
+        rc = getattr(_lib.lib(), name)(
+            *tables, *(() if coef is None else ((ctypes.c_int * 6)(*coef),)), ctypes.c_void_p(scratch.data_ptr()),
             ctypes.c_size_t(scratch_bytes), _lib.ptr(x), nb * n, inp_h, inp_w, mean.ctypes.data_as(ctypes.c_void_p),
             std.ctypes.data_as(ctypes.c_void_p), 1 if nb == 2 else 0, _lib.stream())
-        _lib.check(rc, "cp_preprocess_frames_u8_f32")
+        _lib.check(rc, name)
         return x
 
     def pre_process_batch(self, images, scale, layout="hwc", color="bgr", matrix="bt601"):
@@ -685,20 +339,18 @@ class BaseDetector(object):
         pixel to BGR where it is loaded, with the limited-range `matrix` "bt601" (cv2's COLOR_YUV2BGR_NV12 arithmetic) or "bt709",
         nearest chroma: bit-identical to the call on the HxWx3 BGR host array that conversion gives (csrc/yuv_arith.h).  The
         stream-order and lifetime rules above hold for every plane.  Host YUV arrays are not taken."""
-        images, frames = self._batch_input(images, layout, color, matrix)
+        io = self._io
+        images, frames = io.batch_input(images, layout, color, matrix)
         if not images:
             raise _lib.CenterposeHipError("pre_process_batch needs at least one image")
+        coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+        shapes = [im.shape[0:2] for im in images] if frames is None else [(f.H, f.W) for f in frames]
+        offsets, nbytes = self._batch_layout(shapes) if frames is None else (None, 0)
+        table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale, frames, coef is not None)
+        staging = io.upload_images(images, offsets, nbytes) if frames is None else None
+        table_dev, = io.upload_table([table])
         if frames is not None:
-            shapes = [f[1:3] for f in frames]
-            coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
-            table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, None, list(range(len(frames))), scale, frames, coef is not None)
-            table_dev, = self._upload_table([table])
             return self._launch_frames(table_dev, table, scratch_bytes, inp_h, inp_w, coef), metas
-        shapes = [im.shape[0:2] for im in images]
-        offsets, nbytes = self._batch_layout(shapes)
-        table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale)
-        staging = self._upload_images(images, offsets, nbytes)
-        table_dev, = self._upload_table([table])
         return self._launch_pre(staging, table_dev, table, scratch_bytes, inp_h, inp_w), metas
 
     def _process_batch(self, images):
@@ -742,8 +394,8 @@ class BaseDetector(object):
         returns without `track` and `tracks` = tracker.update(rows, result, sizes) on the call's own rows in input order, frame n being
         stream n: a list of int64 [k, 5] arrays (x1, y1, x2, y2, track_id).  Taken before draw=True paints.  The tracker's download is
         a synchronisation of its own.  Without embed=, or with len(images) != tracker.streams: ValueError, before anything is launched."""
-        given = images
-        images, frames = self._batch_input(images, layout, color, matrix)
+        given, io = images, self._io
+        images, frames = io.batch_input(images, layout, color, matrix)
         coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
         if embed is not None:
             if frames is None:
@@ -766,10 +418,10 @@ class BaseDetector(object):
             if frames is None and images:
                 raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
                                               "there is no CPU fallback")
-            self._check_writable(given, images, color)
+            io.check_writable(given, images, color)
         if not images:
             return torch.empty((0, 0, 56), dtype=torch.float32, device="cuda") if return_device else []
-        shapes = [im.shape[0:2] for im in images] if frames is None else [f[1:3] for f in frames]
+        shapes = [im.shape[0:2] for im in images] if frames is None else [(f.H, f.W) for f in frames]
         offsets, nbytes = self._batch_layout(shapes) if frames is None else (None, 0)
         groups = self._batch_groups(shapes)
         work, parts = [], []
@@ -781,8 +433,8 @@ class BaseDetector(object):
         order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
         if (return_device or draw or embed is not None) and len(groups) > 1:
             parts.append(np.argsort(np.asarray(order, np.int64)).astype(np.int64))       # rides in the one table upload
-        staging = self._upload_images(images, offsets, nbytes) if frames is None else None
-        parts = self._upload_table(parts)
+        staging = io.upload_images(images, offsets, nbytes) if frames is None else None
+        parts = io.upload_table(parts)
         merged = []
         for g, idx in enumerate(groups):
             per_scale = []
@@ -806,7 +458,7 @@ class BaseDetector(object):
         if track is not None:                                    # before anything is painted, like the crops
             tracks = track.update(ordered, result, [(int(w), int(h)) for h, w in shapes])
         if draw:
-            self._draw(images, frames, ordered, color, matrix, None, None)
+            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, None)
         if return_device:
             return ordered if embed is None else (ordered, result) if track is None else (ordered, result, tracks)
         rows = rows.cpu().numpy()                                                               # the one download
@@ -814,63 +466,6 @@ class BaseDetector(object):
         for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
         return results if embed is None else (results, result) if track is None else (results, result, tracks)
-
-    @staticmethod
-    def _check_writable(given, images, color):
-        """Raise unless every frame of a call may be written: every tensor a view without self-overlap (frame_writable), the luma
-        bytes of a plane tuple apart from its chroma bytes, and no tensor given twice."""
-        if isinstance(given, torch.Tensor) and not frame_writable(given.shape, given.stride()):
-            raise _lib.CenterposeHipError("the frames tensor of shape %s and strides %s cannot be written: two of its indices address the "
-                                          "same byte" % (tuple(given.shape), tuple(given.stride())))
-        seen = set()
-        for n, im in enumerate(images):
-            planes = [im] if isinstance(im, torch.Tensor) else list(im)
-            for t in planes:
-                if not frame_writable(t.shape, t.stride()):
-                    raise _lib.CenterposeHipError("frame %d: a view of shape %s and strides %s cannot be written: two of its indices address "
-                                                  "the same byte (expanded or overlapping view)" % (n, tuple(t.shape), tuple(t.stride())))
-                key = (t.data_ptr(), tuple(t.shape), tuple(t.stride()))
-                if key in seen:
-                    raise _lib.CenterposeHipError("frame %d: the same tensor is given twice in one call" % n)
-                seen.add(key)
-            if color in YUV_COLORS and len(planes) > 1:
-                y0, y1 = byte_range(planes[0].data_ptr(), planes[0].shape, planes[0].stride())
-                for t in planes[1:]:
-                    c0, c1 = byte_range(t.data_ptr(), t.shape, t.stride())
-                    if c0 < y1 and y0 < c1:
-                        raise _lib.CenterposeHipError("frame %d: the luma plane and a chroma plane share bytes" % n)
-
-    def _draw(self, images, frames, rows, color, matrix, vis_thresh, style):
-        """cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8 for checked frames (`_frame` / `_yuv_frame` per image) and device rows
-        [N,M,56]: one table upload, two launches in the current stream."""
-        yuv = color in YUV_COLORS
-        style = DrawStyle() if style is None else style
-        if not isinstance(style, DrawStyle):
-            raise _lib.CenterposeHipError("style is a DrawStyle (got %s)" % type(style).__name__)
-        vis_thresh = float(self.cfg.TEST.VIS_THRESH if vis_thresh is None else vis_thresh)
-        N, M = len(images), int(rows.shape[1])
-        if N == 0 or M == 0:
-            return
-        table = np.zeros(N, YUV_FRAME_DESC if yuv else FRAME_DESC)
-        for n, f in enumerate(frames):
-            d = table[n]
-            if yuv:
-                d["y_base"], d["H"], d["W"], d["y_row"], d["y_pix"], d["u_base"], d["v_base"], d["c_row"], d["c_pix"] = f
-            else:
-                d["base"], d["H"], d["W"], d["row_stride"], d["pix_stride"], d["ch_off"] = f
-            d["NH"], d["NW"], d["mid_off"] = d["H"], d["W"], -1
-        table = np.ascontiguousarray(table)
-        rec = style.struct(matrix if yuv else None)
-        L = _lib.lib()
-        L.cp_draw_scratch_bytes.restype = ctypes.c_size_t
-        nbytes = int(L.cp_draw_scratch_bytes(N, M))
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=rows.device)
-        table_dev, = self._upload_table([table])
-        fn = L.cp_draw_rows_yuv_frames_u8 if yuv else L.cp_draw_rows_frames_u8
-        rc = fn(ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), N, ctypes.c_void_p(rows.data_ptr()), M,
-                ctypes.c_float(vis_thresh), rec.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(scratch.data_ptr()),
-                ctypes.c_size_t(nbytes), _lib.stream())
-        _lib.check(rc, "cp_draw_rows_yuv_frames_u8" if yuv else "cp_draw_rows_frames_u8")
 
     def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None):
         """Paint the detections `rows` onto `frames`, in place, on the device, in the current stream -> `frames`.  What is drawn is
@@ -888,28 +483,16 @@ class BaseDetector(object):
         must be a view in which no two indices address one byte (frame_writable: expanded and overlapping views raise), a plane
         tuple's luma bytes must lie apart from its chroma bytes, the same tensor may not be given twice -- and that the frames of one
         call share no bytes otherwise is the caller's promise.  Host arrays raise: there is no CPU fallback."""
-        given = frames
-        images, descs = self._batch_input(frames, layout, color, matrix)
+        given, io = frames, self._io
+        images, descs = io.batch_input(frames, layout, color, matrix)
         if descs is None and images:
             raise _lib.CenterposeHipError("draw_results paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
                                           "there is no CPU fallback")
-        if isinstance(rows, np.ndarray) or not isinstance(rows, torch.Tensor):
-            raise _lib.CenterposeHipError("rows must be a CUDA float32 tensor [N, M, 56] on the device (got %s): there is no CPU fallback"
-                                          % type(rows).__name__)
-        if rows.dim() == 2:
-            rows = rows.unsqueeze(0)
-        if rows.dim() != 3 or rows.shape[2] != 56:
-            raise _lib.CenterposeHipError("rows must be [N, M, 56] (or [M, 56] for one frame), got shape %s" % (tuple(rows.shape),))
-        if not rows.is_cuda:
-            raise _lib.CenterposeHipError("rows on %s: they must be on the model's GPU; there is no CPU fallback" % rows.device)
-        if rows.device != self._model_device():
-            raise _lib.CenterposeHipError("rows on %s, the model is on %s" % (rows.device, self._model_device()))
-        if rows.dtype != torch.float32:
-            raise _lib.CenterposeHipError("rows must be float32 (got %s)" % rows.dtype)
-        if rows.shape[0] != len(images):
-            raise _lib.CenterposeHipError("rows hold %d blocks for %d frames" % (rows.shape[0], len(images)))
-        self._check_writable(given, images, color)
-        self._draw(images, descs or [], rows.detach().contiguous(), color, matrix, vis_thresh, style)
+        rows = check_rows(rows, len(images), io.device, "the model is on %s",
+                          on_host="rows on %s: they must be on the model's GPU; there is no CPU fallback")
+        io.check_writable(given, images, color)
+        draw_rows(io, descs or [], rows.detach().contiguous(), color, matrix, self.cfg.TEST.VIS_THRESH if vis_thresh is None else vis_thresh,
+                  style)
         return given
 
     def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):
@@ -1118,7 +701,7 @@ class MultiPoseDetector(BaseDetector):
         bit-identical to post_process(dets[n:n + 1], metas[n], scale)[1].  No download."""
         if dets.dim() != 3 or dets.shape[0] != len(metas):
             raise _lib.CenterposeHipError("post_process_batch needs dets [N,K,56] and N metas")
-        inv_dev, = self._upload_table([self._inverse_affines(metas)])
+        inv_dev, = self._io.upload_table([self._inverse_affines(metas)])
         return self._launch_post(dets, inv_dev.view(torch.float64).view(1, len(metas), 6), scale)
 
     def merge_outputs_batch(self, detections):

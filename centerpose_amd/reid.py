@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib, nets
-from .detector import FRAME_DESC, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, BaseDetector
 from .engine import Engine
+from .frames import YUV_COLORS, YUV_MATRICES, FrameIO, check_rows, identity_table
 
 # cp_reid_norm (include/centerpose_hip.h)
 REID_NORM = np.dtype([("scale", "<f4"), ("mean", "<f4", (3,)), ("std", "<f4", (3,)), ("rgb", "<i4")])
@@ -29,16 +29,6 @@ def load_reid_state_dict(path):
     """The reference's checkpoint format (feature_extractor.py:11: torch.load(path)['net_dict']), tensors only: nothing else is
     unpickled."""
     return torch.load(path, map_location="cpu", weights_only=True)["net_dict"]
-
-
-class _Frames(BaseDetector):
-    """BaseDetector's device-frame plumbing (`_batch_input`, `_frame`, `_yuv_frame`, `_upload_table`) without a model behind it."""
-
-    def __init__(self, device):
-        self._device = device
-
-    def _model_device(self):
-        return self._device
 
 
 def _holds_host_array(frames):
@@ -91,7 +81,7 @@ class ReidExtractor:
         self.device = self.engine.device if self.engine.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         self.norm = np.zeros(1, REID_NORM)
         self.norm["scale"], self.norm["mean"], self.norm["std"], self.norm["rgb"] = scale, mean, std, CHANNEL_ORDERS.index(channel_order)
-        self._io = _Frames(self.device)
+        self._io = FrameIO(self.device)
         with torch.cuda.device(self.device):
             self.engine.capture()      # the one-off capture synchronises: here, not in the first embed
 
@@ -106,24 +96,12 @@ class ReidExtractor:
         if _holds_host_array(frames):
             raise ValueError("embed takes its crops from device frames (CUDA uint8 tensors): host arrays are not read, there is no "
                              "CPU fallback")
-        images, descs = self._io._batch_input(frames, layout, color, matrix)
-        if not isinstance(rows, torch.Tensor):
-            raise _lib.CenterposeHipError("rows must be a CUDA float32 tensor [N, M, 56] on the device (got %s): there is no CPU fallback"
-                                          % type(rows).__name__)
-        if rows.dim() == 2:
-            rows = rows.unsqueeze(0)
-        if rows.dim() != 3 or rows.shape[2] != 56:
-            raise _lib.CenterposeHipError("rows must be [N, M, 56] (or [M, 56] for one frame), got shape %s" % (tuple(rows.shape),))
-        if not rows.is_cuda or rows.device != self.device:
-            raise _lib.CenterposeHipError("rows on %s, the re-id plan is on %s; there is no CPU fallback" % (rows.device, self.device))
-        if rows.dtype != torch.float32:
-            raise _lib.CenterposeHipError("rows must be float32 (got %s)" % rows.dtype)
-        if rows.shape[0] != len(images):
-            raise _lib.CenterposeHipError("rows hold %d blocks for %d frames" % (rows.shape[0], len(images)))
+        images, descs = self._io.batch_input(frames, layout, color, matrix)
+        rows = check_rows(rows, len(images), self.device, "the re-id plan is on %s; there is no CPU fallback")
         return self._embed(descs or [], rows.detach().contiguous(), color, matrix, vis_thresh)
 
     def _embed(self, descs, rows, color, matrix, vis_thresh):
-        """select + crop + one replay for checked frames (`_frame` / `_yuv_frame` per frame) and device rows [N, M, 56]."""
+        """select + crop + one replay for checked frames (a frames.Frame / YuvFrame per frame) and device rows [N, M, 56]."""
         yuv = color in YUV_COLORS
         N, M, cap = len(descs), int(rows.shape[1]), self.capacity
         if N < 1:
@@ -133,21 +111,13 @@ class ReidExtractor:
                              "a larger capacity)" % (N, cap))
         if N * M > 1 << 24:
             raise ValueError("%d x %d rows are too many for one call (at most 2^24)" % (N, M))
-        table = np.zeros(N, YUV_FRAME_DESC if yuv else FRAME_DESC)
-        for n, f in enumerate(descs):
-            d = table[n]
-            if yuv:
-                d["y_base"], d["H"], d["W"], d["y_row"], d["y_pix"], d["u_base"], d["v_base"], d["c_row"], d["c_pix"] = f
-            else:
-                d["base"], d["H"], d["W"], d["row_stride"], d["pix_stride"], d["ch_off"] = f
-            d["NH"], d["NW"], d["mid_off"] = d["H"], d["W"], -1
-        table = np.ascontiguousarray(table)
+        table = identity_table(descs, yuv)
         L = _lib.lib()
         vp = ctypes.c_void_p
         with torch.cuda.device(self.device):
             slots = torch.empty((cap,), dtype=torch.int32, device=self.device)
             counts = torch.empty((N,), dtype=torch.int32, device=self.device)
-            table_dev, = self._io._upload_table([table])
+            table_dev, = self._io.upload_table([table])
             th, thr = table.ctypes.data_as(vp), ctypes.c_float(float(vis_thresh))
             _lib.check(L.cp_reid_select_rows(vp(table_dev.data_ptr()), th, int(yuv), N, vp(rows.data_ptr()), M, thr, cap,
                                              vp(slots.data_ptr()), vp(counts.data_ptr()), _lib.stream()), "cp_reid_select_rows")

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .reid import ReidResult, _Frames
+from .frames import FrameIO, check_rows
+from .reid import ReidResult
 
 DIM = 512
 MAX_BUDGET, MAX_TCAP = 128, 1024                 # TH_MAX_BUDGET, TH_MAX_TCAP (csrc/track_host.h)
@@ -143,7 +144,7 @@ class DeepSortTracker:
             self.gallery = torch.zeros((streams * max_tracks, budget, DIM), dtype=torch.float32, device=self.device)
             self.ginv = torch.zeros((streams * max_tracks, budget), dtype=torch.float32, device=self.device)
             self.out = torch.empty((streams * max_tracks * self.q + streams * self.q * 5,), dtype=torch.float32, device=self.device)
-            self._io = _Frames(self.device)
+            self._io = FrameIO(self.device)
 
     # ------------------------------------------------------------------ host logic
     def begin(self):
@@ -278,8 +279,9 @@ class DeepSortTracker:
     def _check(self, rows, result, sizes):
         if not isinstance(result, ReidResult):
             raise ValueError("result must be the ReidResult of the call's rows (got %s)" % type(result).__name__)
-        for name, t, dtype in (("rows", rows, torch.float32), ("result.features", result.features, torch.float32),
-                               ("result.slots", result.slots, torch.int32)):
+        rows = check_rows(rows, None, self.device, "the gallery is on %s; there is no CPU fallback", what="a CUDA tensor", one="stream",
+                          f32="torch.float32")
+        for name, t, dtype in (("result.features", result.features, torch.float32), ("result.slots", result.slots, torch.int32)):
             if not isinstance(t, torch.Tensor):
                 raise _lib.CenterposeHipError("%s must be a CUDA tensor on the device (got %s): there is no CPU fallback"
                                               % (name, type(t).__name__))
@@ -289,10 +291,6 @@ class DeepSortTracker:
                 raise _lib.CenterposeHipError("%s must be %s (got %s)" % (name, dtype, t.dtype))
         if self.device is None:
             raise _lib.CenterposeHipError("this tracker was built without a device (device=None): update needs the gallery on the GPU")
-        if rows.dim() == 2:
-            rows = rows.unsqueeze(0)
-        if rows.dim() != 3 or rows.shape[2] != 56:
-            raise _lib.CenterposeHipError("rows must be [N, M, 56] (or [M, 56] for one stream), got shape %s" % (tuple(rows.shape),))
         if rows.shape[0] != self.streams:
             raise ValueError("rows hold %d frames, the tracker has %d streams: frame n of a call belongs to stream n"
                              % (rows.shape[0], self.streams))
@@ -320,14 +318,14 @@ class DeepSortTracker:
         L, vp = _lib.lib(), ctypes.c_void_p
         features = result.features.detach().contiguous()
         with torch.cuda.device(self.device):
-            glen_dev, = self._io._upload_table([glen])
+            glen_dev, = self._io.upload_table([glen])
             _lib.check(L.cp_track_cost_f32(vp(self.gallery.data_ptr()), vp(self.ginv.data_ptr()), vp(glen_dev.data_ptr()),
                                            vp(features.data_ptr()), vp(result.slots.data_ptr()), vp(rows.data_ptr()), M, S, Tcap,
                                            self.budget, q, vp(self.out.data_ptr()), _lib.stream()), "cp_track_cost_f32")
             host = self.out.cpu().numpy()                                          # the one download: costs and boxes
             outs, table = self.associate(host[:S * Tcap * q], host[S * Tcap * q:], sizes)
             if len(table):
-                table_dev, = self._io._upload_table([table])
+                table_dev, = self._io.upload_table([table])
                 _lib.check(L.cp_track_append_f32(vp(self.gallery.data_ptr()), vp(self.ginv.data_ptr()), vp(features.data_ptr()),
                                                  vp(table_dev.data_ptr()), len(table), self.budget, _lib.stream()), "cp_track_append_f32")
         return outs

@@ -47,7 +47,7 @@ def _detector(monkeypatch, arch="dla_34", **overrides):
     det.mean = np.array(det.cfg.DATASET.MEAN, dtype=np.float32).reshape(1, 1, 3)
     det.std = np.array(det.cfg.DATASET.STD, dtype=np.float32).reshape(1, 1, 3)
     log = []
-    det._staging_buffers = {"images": _FakeStaging(log, "images"), "table": _FakeStaging(log, "table")}
+    det._io.buffers.update(images=_FakeStaging(log, "images"), table=_FakeStaging(log, "table"))
     nb = 2 if det.cfg.TEST.FLIP_TEST else 1
 
     def launch_pre(staging, table_dev, table, scratch_bytes, inp_h, inp_w):

@@ -261,7 +261,7 @@ def test_alignment_and_append_refusals():
 
 
 def test_tracker_refusals_without_a_device():
-    from centerpose_amd import reid, track
+    from centerpose_amd import detector, reid, track
     from centerpose_amd._lib import CenterposeHipError
     for bad in (dict(capacity=1, streams=2), dict(capacity=4, streams=0), dict(capacity=4, max_tracks=0), dict(capacity=4, max_tracks=1025),
                 dict(capacity=4, budget=0), dict(capacity=4, budget=129)):
@@ -281,7 +281,7 @@ def test_tracker_refusals_without_a_device():
         trk.associate(np.zeros((2, 64, 2)), np.zeros((2, 2, 5)), [(64, 48)])
     # run_batch(track=) without embed=: refused before anything else happens (a detector without a model is enough to get there)
     with pytest.raises(ValueError, match="needs embed"):
-        reid._Frames(torch.device("cpu")).run_batch([], track=trk)
+        object.__new__(detector.BaseDetector).run_batch([], track=trk)
 
 
 # ---------------------------------------------------------------- 6. symbols
