@@ -39,6 +39,20 @@ struct DaStyle {
 };
 static_assert(sizeof(DaStyle) == 156, "cp_draw_style is 156 bytes");
 
+// mirror of cp_draw_id_palette: a row whose id is >= 0 paints all of its primitives in colors[id % count]
+#define DA_MAX_ID_COLORS 64
+struct DaIdPalette {
+    int count;              // 1..64
+    unsigned char colors[DA_MAX_ID_COLORS][4];      // bytes 0..2 as in DaStyle's palette; byte 3 is not used
+};
+static_assert(sizeof(DaIdPalette) == 260, "cp_draw_id_palette is 260 bytes");
+
+// what primitive l of a row stores: the style's colour, or with row ids the identity colour of a row whose id is >= 0
+DA_HD const unsigned char* da_color(const DaStyle& st, const DaIdPalette* idp, int id, int l)
+{
+    return (idp && id >= 0) ? idp->colors[id % idp->count] : st.palette[l];
+}
+
 // box: (x0, y0) <= (x1, y1), sorted; limb: P = (x0, y0), Q = (x1, y1); joint: P = Q = (x0, y0)
 struct DaPrim { int x0, y0, x1, y1; };
 

@@ -37,6 +37,12 @@ struct DrYuvFrameDesc {
 };
 static_assert(sizeof(DrYuvFrameDesc) == 136, "cp_yuv_frame_desc is 136 bytes");
 
+// the descriptor type of a painter instantiated for BGR / RGB frames (false) or YUV frames (true)
+template <bool YUV>
+struct DrDesc { typedef DrFrameDesc type; };
+template <>
+struct DrDesc<true> { typedef DrYuvFrameDesc type; };
+
 // scratch of one call: per row a header (bounding box, mask of existing primitives), then the primitive records of all rows
 struct DrRowHeader { int x0, y0, x1, y1; unsigned long long mask; unsigned long long pad; };
 static_assert(sizeof(DrRowHeader) == 32, "row header is 32 bytes");
@@ -74,6 +80,14 @@ inline int dr_check_call(const char* who, int N, int M, float vis_thresh, const 
     DR_CHECK(style->joint_radius >= -1 && style->joint_radius <= DA_MAX_REACH, "%s: joint_radius %d outside -1..%d", who,
              style->joint_radius, DA_MAX_REACH);
     *noop = N == 0 || M == 0;
+    return 0;
+}
+
+// the two arguments of the identity-coloured forms come together or not at all
+inline int dr_check_ids(const char* who, const int* row_ids, const DaIdPalette* idp, char* err, size_t errn)
+{
+    DR_CHECK(row_ids && idp, "%s: null row_ids or id palette", who);
+    DR_CHECK(idp->count >= 1 && idp->count <= DA_MAX_ID_COLORS, "%s: %d id colours outside 1..%d", who, idp->count, DA_MAX_ID_COLORS);
     return 0;
 }
 
@@ -138,23 +152,28 @@ inline void dr_paint_row(const float* row, const DaStyle& s, int H, int W, Put p
 }
 
 // HOST painter over cp_frame_desc descriptors with host addresses
+// (ids: with row_ids int [N, M] and an id palette, a row whose id is >= 0 stores colors[id % count] for all of its primitives)
 inline int dr_draw_frames_host(const DrFrameDesc* table, int N, const float* rows, int M, float vis_thresh, const DaStyle* style, char* err,
-                               size_t errn)
+                               size_t errn, bool ids = false, const int* row_ids = nullptr, const DaIdPalette* idp = nullptr)
 {
-    const char* who = "draw_rows_frames_host";
+    const char* who = ids ? "draw_rows_ids_frames_host" : "draw_rows_frames_host";
     bool noop;
     if (int rc = dr_check_call(who, N, M, vis_thresh, style, &noop, err, errn)) return rc;
     if (noop) return 0;
     DR_CHECK(table && rows, "%s: null pointer", who);
+    if (ids)
+        if (int rc = dr_check_ids(who, row_ids, idp, err, errn)) return rc;
     if (int rc = dr_check_frames(who, table, N, err, errn)) return rc;
     for (int n = 0; n < N; ++n) {
         const DrFrameDesc& d = table[n];
         for (int m = 0; m < M; ++m) {
             const float* row = rows + ((size_t)n * M + m) * DA_ROW;
             if (!da_live(row, vis_thresh)) continue;
+            const int id = ids ? row_ids[(size_t)n * M + m] : -1;
             dr_paint_row(row, *style, d.H, d.W, [&](int x, int y, int l) {
                 unsigned char* p = d.base + (long long)y * d.row_stride + (long long)x * d.pix_stride;
-                for (int k = 0; k < 3; ++k) p[d.ch_off[k]] = style->palette[l][k];
+                const unsigned char* c = da_color(*style, ids ? idp : nullptr, id, l);
+                for (int k = 0; k < 3; ++k) p[d.ch_off[k]] = c[k];
             });
         }
     }
@@ -164,24 +183,28 @@ inline int dr_draw_frames_host(const DrFrameDesc* table, int N, const float* row
 // HOST painter over cp_yuv_frame_desc descriptors with host addresses; palette entries are (Y, U, V).  Every covered pixel stores its
 // luma and the chroma sample of its 2x2 block, so the sample ends with the colour of the last primitive that covers any of the four.
 inline int dr_draw_yuv_frames_host(const DrYuvFrameDesc* table, int N, const float* rows, int M, float vis_thresh, const DaStyle* style,
-                                   char* err, size_t errn)
+                                   char* err, size_t errn, bool ids = false, const int* row_ids = nullptr, const DaIdPalette* idp = nullptr)
 {
-    const char* who = "draw_rows_yuv_frames_host";
+    const char* who = ids ? "draw_rows_ids_yuv_frames_host" : "draw_rows_yuv_frames_host";
     bool noop;
     if (int rc = dr_check_call(who, N, M, vis_thresh, style, &noop, err, errn)) return rc;
     if (noop) return 0;
     DR_CHECK(table && rows, "%s: null pointer", who);
+    if (ids)
+        if (int rc = dr_check_ids(who, row_ids, idp, err, errn)) return rc;
     if (int rc = dr_check_yuv_frames(who, table, N, err, errn)) return rc;
     for (int n = 0; n < N; ++n) {
         const DrYuvFrameDesc& d = table[n];
         for (int m = 0; m < M; ++m) {
             const float* row = rows + ((size_t)n * M + m) * DA_ROW;
             if (!da_live(row, vis_thresh)) continue;
+            const int id = ids ? row_ids[(size_t)n * M + m] : -1;
             dr_paint_row(row, *style, d.H, d.W, [&](int x, int y, int l) {
                 const long long c = (long long)(y >> 1) * d.c_row + (long long)(x >> 1) * d.c_pix;
-                d.y_base[(long long)y * d.y_row + (long long)x * d.y_pix] = style->palette[l][0];
-                d.u_base[c] = style->palette[l][1];
-                d.v_base[c] = style->palette[l][2];
+                const unsigned char* col = da_color(*style, ids ? idp : nullptr, id, l);
+                d.y_base[(long long)y * d.y_row + (long long)x * d.y_pix] = col[0];
+                d.u_base[c] = col[1];
+                d.v_base[c] = col[2];
             });
         }
     }

@@ -50,15 +50,17 @@ __global__ __launch_bounds__(DR_THREADS) void draw_build_kernel(const float* __r
     if (lane == 0) hdr[r] = DrRowHeader{x0, y0, x1, y1, mask, 0};
 }
 
-template <bool YUV>
-struct DrDesc { typedef DrFrameDesc type; };
+// IDS: the identity-coloured form -- one more pointer and a palette, consulted only where a winner's colour is looked up
+struct DrNoIds {};
+template <bool IDS>
+struct DrIds { typedef DrNoIds type; };
 template <>
-struct DrDesc<true> { typedef DrYuvFrameDesc type; };
+struct DrIds<true> { typedef DaIdPalette type; };
 
-template <bool YUV>
+template <bool YUV, bool IDS>
 __global__ __launch_bounds__(DR_THREADS) void draw_raster_kernel(const typename DrDesc<YUV>::type* __restrict__ table,
                                                                  const DrRowHeader* __restrict__ hdr, const DaPrim* __restrict__ prims, int M,
-                                                                 DaStyle st)
+                                                                 DaStyle st, const int* __restrict__ row_ids, typename DrIds<IDS>::type idp)
 {
     constexpr int S = YUV ? 2 : 1, Q = S * S;
     const typename DrDesc<YUV>::type& d = table[blockIdx.z];
@@ -119,6 +121,14 @@ __global__ __launch_bounds__(DR_THREADS) void draw_raster_kernel(const typename 
         __syncthreads();                                       // the list is rewritten by the next chunk
     }
 
+    // what the winner with paint index w stores
+    auto color = [&](int w) -> const unsigned char* {
+        if constexpr (IDS)
+            return da_color(st, &idp, row_ids[(size_t)blockIdx.z * M + w / DA_PRIMS], w % DA_PRIMS);
+        else
+            return st.palette[w % DA_PRIMS];
+    };
+
     if constexpr (YUV) {
         const DrYuvFrameDesc& f = d;
         int top = -1;
@@ -126,21 +136,22 @@ __global__ __launch_bounds__(DR_THREADS) void draw_raster_kernel(const typename 
         for (int q = 0; q < Q; ++q) {
             if (win[q] < 0) continue;
             const int x = px + (q % S), y = py + (q / S);
-            f.y_base[(long long)y * f.y_row + (long long)x * f.y_pix] = st.palette[win[q] % DA_PRIMS][0];
+            f.y_base[(long long)y * f.y_row + (long long)x * f.y_pix] = color(win[q])[0];
             top = max(top, win[q]);
         }
         if (top >= 0) {
             const long long c = (long long)(py >> 1) * f.c_row + (long long)(px >> 1) * f.c_pix;
-            f.u_base[c] = st.palette[top % DA_PRIMS][1];
-            f.v_base[c] = st.palette[top % DA_PRIMS][2];
+            const unsigned char* col = color(top);
+            f.u_base[c] = col[1];
+            f.v_base[c] = col[2];
         }
     } else {
         const DrFrameDesc& f = d;
         if (win[0] >= 0) {
             unsigned char* p = f.base + (long long)py * f.row_stride + (long long)px * f.pix_stride;
-            const int l = win[0] % DA_PRIMS;
+            const unsigned char* col = color(win[0]);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p[f.ch_off[k]] = st.palette[l][k];
+            for (int k = 0; k < 3; ++k) p[f.ch_off[k]] = col[k];
         }
     }
 }
@@ -171,14 +182,16 @@ extern "C" int cp_draw_rows_yuv_frames_host(const void* table_host, int N, const
     return 0;
 }
 
-template <bool YUV>
+template <bool YUV, bool IDS>
 static int dr_launch(const char* who, const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
-                     const DaStyle* style, void* scratch, size_t scratch_bytes, void* stream)
+                     const DaStyle* style, void* scratch, size_t scratch_bytes, void* stream, const int* row_ids = nullptr,
+                     const DaIdPalette* idp = nullptr)
 {
     typedef typename DrDesc<YUV>::type Desc;
     bool noop;
     DR_FORWARD(dr_check_call(who, N, M, vis_thresh, style, &noop, err, errn));
     if (noop) return 0;
+    if constexpr (IDS) DR_FORWARD(dr_check_ids(who, row_ids, idp, err, errn));
     CP_CHECK_ARG(table && table_host && rows && scratch, "%s: null pointer", who);
     CP_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", who);
     CP_CHECK_ARG(scratch_bytes >= dr_scratch_bytes(N, M), "%s: scratch of %zu bytes, %zu needed (cp_draw_scratch_bytes)", who, scratch_bytes,
@@ -203,21 +216,65 @@ static int dr_launch(const char* who, const void* table, const void* table_host,
                        style->box_thickness, style->limb_radius, style->joint_radius, hdr, prims);
     CP_CHECK_LAUNCH("draw_build_kernel");
     const int tile = DR_TILE * (YUV ? 2 : 1);
-    hipLaunchKernelGGL(draw_raster_kernel<YUV>, dim3((unsigned)cp_cdiv(maxW, tile), (unsigned)cp_cdiv(maxH, tile), (unsigned)N), dim3(DR_THREADS), 0, s,
-                       (const Desc*)table, (const DrRowHeader*)hdr, (const DaPrim*)prims, M, *style);
+    const dim3 grid((unsigned)cp_cdiv(maxW, tile), (unsigned)cp_cdiv(maxH, tile), (unsigned)N);
+    if constexpr (IDS) {
+        hipLaunchKernelGGL((draw_raster_kernel<YUV, true>), grid, dim3(DR_THREADS), 0, s, (const Desc*)table, (const DrRowHeader*)hdr,
+                           (const DaPrim*)prims, M, *style, row_ids, *idp);
+    } else {
+        hipLaunchKernelGGL((draw_raster_kernel<YUV, false>), grid, dim3(DR_THREADS), 0, s, (const Desc*)table, (const DrRowHeader*)hdr,
+                           (const DaPrim*)prims, M, *style, (const int*)nullptr, DrNoIds{});
+    }
     CP_CHECK_LAUNCH("draw_raster_kernel");
-    cp_note_kernel(YUV ? "draw_raster_kernel<yuv>" : "draw_raster_kernel<bgr>");
+    if constexpr (IDS)
+        cp_note_kernel(YUV ? "draw_raster_kernel<yuv,ids>" : "draw_raster_kernel<bgr,ids>");
+    else
+        cp_note_kernel(YUV ? "draw_raster_kernel<yuv>" : "draw_raster_kernel<bgr>");
     return 0;
 }
 
 extern "C" int cp_draw_rows_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
                                       const void* style, void* scratch, size_t scratch_bytes, void* stream)
 {
-    return dr_launch<false>("draw_rows_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch, scratch_bytes, stream);
+    return dr_launch<false, false>("draw_rows_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch, scratch_bytes,
+                                   stream);
 }
 
 extern "C" int cp_draw_rows_yuv_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
                                           const void* style, void* scratch, size_t scratch_bytes, void* stream)
 {
-    return dr_launch<true>("draw_rows_yuv_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch, scratch_bytes, stream);
+    return dr_launch<true, false>("draw_rows_yuv_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch, scratch_bytes,
+                                  stream);
+}
+
+// the identity-coloured forms: the same launches with row_ids DEVICE int [N, M] and a HOST cp_draw_id_palette
+extern "C" int cp_draw_rows_ids_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                                          const void* style, void* scratch, size_t scratch_bytes, const int* row_ids, const void* id_palette,
+                                          void* stream)
+{
+    return dr_launch<false, true>("draw_rows_ids_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch,
+                                  scratch_bytes, stream, row_ids, (const DaIdPalette*)id_palette);
+}
+
+extern "C" int cp_draw_rows_ids_yuv_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                                              const void* style, void* scratch, size_t scratch_bytes, const int* row_ids,
+                                              const void* id_palette, void* stream)
+{
+    return dr_launch<true, true>("draw_rows_ids_yuv_frames", table, table_host, N, rows, M, vis_thresh, (const DaStyle*)style, scratch,
+                                 scratch_bytes, stream, row_ids, (const DaIdPalette*)id_palette);
+}
+
+extern "C" int cp_draw_rows_ids_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                            const int* row_ids, const void* id_palette)
+{
+    DR_FORWARD(dr_draw_frames_host((const DrFrameDesc*)table_host, N, rows, M, vis_thresh, (const DaStyle*)style, err, errn, true, row_ids,
+                                   (const DaIdPalette*)id_palette));
+    return 0;
+}
+
+extern "C" int cp_draw_rows_ids_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                                const int* row_ids, const void* id_palette)
+{
+    DR_FORWARD(dr_draw_yuv_frames_host((const DrYuvFrameDesc*)table_host, N, rows, M, vis_thresh, (const DaStyle*)style, err, errn, true, row_ids,
+                                       (const DaIdPalette*)id_palette));
+    return 0;
 }

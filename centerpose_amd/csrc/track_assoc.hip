@@ -118,6 +118,23 @@ __global__ __launch_bounds__(TH_LANES) void track_append_kernel(float* __restric
     if (tid == 0) ginv[row] = th_inv_norm(p[0]);
 }
 
+// per-row track ids, two launches so that nothing is ordered between workgroups inside one: every row gets -1, then every used and
+// matched detection slot writes its id into its row.  Slots address distinct rows; a slot outside [0, S * M) is skipped.
+__global__ __launch_bounds__(TA_THREADS) void track_row_ids_fill_kernel(int* __restrict__ row_ids, int total)
+{
+    const int r = blockIdx.x * TA_THREADS + threadIdx.x;
+    if (r < total) row_ids[r] = -1;
+}
+
+__global__ __launch_bounds__(TA_THREADS) void track_row_ids_scatter_kernel(const int* __restrict__ slots, const int* __restrict__ slot_ids,
+                                                                            int n, int total, int* __restrict__ row_ids)
+{
+    const int i = blockIdx.x * TA_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int v = slots[i], id = slot_ids[i];
+    if (v >= 0 && v < total && id >= 0) row_ids[v] = id;
+}
+
 #define TA_FORWARD(call)                          \
     do {                                          \
         char err[256];                            \
@@ -178,5 +195,28 @@ extern "C" int cp_track_append_f32(float* gallery, float* ginv, const float* fea
     hipLaunchKernelGGL(track_append_kernel, dim3((unsigned)n), dim3(TH_LANES), 0, (hipStream_t)stream, gallery, ginv, features, table, budget);
     CP_CHECK_LAUNCH("track_append_kernel");
     cp_note_kernel("track_append_kernel");
+    return 0;
+}
+
+extern "C" int cp_track_row_ids_host(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids)
+{
+    TA_FORWARD(th_row_ids_host(slots, slot_ids, capacity, S, q, M, row_ids, err, errn));
+    return 0;
+}
+
+extern "C" int cp_track_row_ids(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids, void* stream)
+{
+    const char* who = "track_row_ids";
+    TA_FORWARD(th_check_row_ids(who, capacity, S, q, M, err, errn));
+    CP_CHECK_ARG(slots && slot_ids && (row_ids || M == 0), "%s: null pointer", who);
+    const int total = S * M, n = S * q;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(track_row_ids_fill_kernel, dim3((unsigned)cp_cdiv(total, TA_THREADS)), dim3(TA_THREADS), 0, (hipStream_t)stream, row_ids,
+                       total);
+    CP_CHECK_LAUNCH("track_row_ids_fill_kernel");
+    hipLaunchKernelGGL(track_row_ids_scatter_kernel, dim3((unsigned)cp_cdiv(n, TA_THREADS)), dim3(TA_THREADS), 0, (hipStream_t)stream, slots,
+                       slot_ids, n, total, row_ids);
+    CP_CHECK_LAUNCH("track_row_ids_scatter_kernel");
+    cp_note_kernel("track_row_ids_scatter_kernel");
     return 0;
 }

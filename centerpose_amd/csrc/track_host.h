@@ -124,6 +124,34 @@ static inline int th_append_host(float* gallery, float* ginv, const float* featu
     return 0;
 }
 
+// Per-row track ids: row_ids[S, M] = -1 everywhere, then row_ids[slots[i]] = slot_ids[i] for every detection slot i < S * q that is used
+// (slots[i] >= 0) and matched (slot_ids[i] >= 0).  What both entry points refuse (pointers and slot values apart):
+static inline int th_check_row_ids(const char* who, int capacity, int S, int q, int M, char* err, size_t errn)
+{
+    if (S < 1 || S > 65535) TH_FAIL("%s: S = %d outside 1..65535", who, S);
+    if (q < 1) TH_FAIL("%s: q = %d: every stream needs at least one detection slot", who, q);
+    if (M < 0) TH_FAIL("%s: M = %d is negative", who, M);
+    if ((long long)S * q > (1ll << 24)) TH_FAIL("%s: S * q = %lld detection slots exceed 2^24", who, (long long)S * q);
+    if ((long long)capacity < (long long)S * q) TH_FAIL("%s: capacity %d holds fewer than S * q = %lld slots", who, capacity, (long long)S * q);
+    if ((long long)S * M > (1ll << 24)) TH_FAIL("%s: S * M = %lld rows exceed 2^24", who, (long long)S * M);
+    return 0;
+}
+
+static inline int th_row_ids_host(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids, char* err,
+                                  size_t errn)
+{
+    const char* who = "track_row_ids_host";
+    if (int rc = th_check_row_ids(who, capacity, S, q, M, err, errn)) return rc;
+    if (!slots || !slot_ids || (!row_ids && M > 0)) TH_FAIL("%s: null pointer", who);
+    const int total = S * M;
+    for (int i = 0; i < S * q; ++i)
+        if (slots[i] < -1 || slots[i] >= total) TH_FAIL("%s: slot %d holds row %d outside -1..%d", who, i, slots[i], total - 1);
+    for (int r = 0; r < total; ++r) row_ids[r] = -1;
+    for (int i = 0; i < S * q; ++i)
+        if (slots[i] >= 0 && slot_ids[i] >= 0) row_ids[slots[i]] = slot_ids[i];
+    return 0;
+}
+
 // Rectangular minimum-cost assignment on float64: shortest augmenting paths with row / column potentials (the Hungarian method in
 // its O(n^2 m) form; Kuhn 1955, Munkres 1957, Jonker & Volgenant 1987 for the potentials).  min(rows, cols) pairs are made;
 // row_to_col[r] is the column of row r or -1.  Entries must be finite.

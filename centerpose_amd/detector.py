@@ -35,6 +35,7 @@ from . import _lib
 from .decode import multi_pose_decode
 # frames.py and draw.py hold what used to be defined here: besides what this module uses, the names callers import from it stay
 from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv      # noqa: F401
+from .draw import TRACK_ITEM, TRACK_PALETTE, TrackStyle, draw_track_items                                            # noqa: F401
 from .frames import (FRAME_DESC, PRE_DESC, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO, _check_layout, byte_range,      # noqa: F401
                      check_rows, frame_geometry, frame_writable, identity_table, yuv_frame_geometry)
 from .model import create_model, load_model
@@ -393,7 +394,12 @@ class BaseDetector(object):
         track=tracker (a track.DeepSortTracker; needs embed=): -> (rows, result, tracks) with `rows` and `result` exactly what the call
         returns without `track` and `tracks` = tracker.update(rows, result, sizes) on the call's own rows in input order, frame n being
         stream n: a list of int64 [k, 5] arrays (x1, y1, x2, y2, track_id).  Taken before draw=True paints.  The tracker's download is
-        a synchronisation of its own.  Without embed=, or with len(images) != tracker.streams: ValueError, before anything is launched."""
+        a synchronisation of its own.  Without embed=, or with len(images) != tracker.streams: ValueError, before anything is launched.
+        draw="tracks" (needs track=; ValueError before anything is launched otherwise): after the crops and tracker.update the frames
+        are painted with the tracker's result -- draw_results with the call's rows at TEST.VIS_THRESH and row_ids =
+        track.row_ids(result, M), so that every matched pose takes its identity colour, then draw_tracks with `tracks` on top, both
+        with their default styles.  The return value is exactly what it is without `draw`; the painting adds no synchronisation and
+        one table upload per painting call."""
         given, io = images, self._io
         images, frames = io.batch_input(images, layout, color, matrix)
         coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
@@ -414,6 +420,10 @@ class BaseDetector(object):
                 raise ValueError("the tracker was built for capacity %d, the extractor has %d" % (track.capacity, embed.capacity))
             if track.device != embed.device:
                 raise _lib.CenterposeHipError("the tracker is on %s, the extractor is on %s" % (track.device, embed.device))
+        if isinstance(draw, str) and draw != "tracks":
+            raise ValueError("draw=%r: False, True or \"tracks\"" % (draw,))
+        if draw == "tracks" and track is None:
+            raise ValueError("draw=\"tracks\" needs track=: it paints the tracker's identities")
         if draw:
             if frames is None and images:
                 raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -457,7 +467,11 @@ class BaseDetector(object):
         tracks = None
         if track is not None:                                    # before anything is painted, like the crops
             tracks = track.update(ordered, result, [(int(w), int(h)) for h, w in shapes])
-        if draw:
+        if draw == "tracks":
+            ordered = ordered.contiguous()
+            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, None, row_ids=track.row_ids(result, int(ordered.shape[1])))
+            draw_track_items(io, frames, tracks, color, matrix, None)
+        elif draw:
             draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, None)
         if return_device:
             return ordered if embed is None else (ordered, result) if track is None else (ordered, result, tracks)
@@ -467,7 +481,8 @@ class BaseDetector(object):
             results[i] = {1: rows[r].tolist()}
         return results if embed is None else (results, result) if track is None else (results, result, tracks)
 
-    def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None):
+    def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None, row_ids=None,
+                     id_palette=None):
         """Paint the detections `rows` onto `frames`, in place, on the device, in the current stream -> `frames`.  What is drawn is
         what the reference's show_results draws, without the text: per row with score > vis_thresh (default cfg.TEST.VIS_THRESH) the
         box, the limbs whose two joints both score > 0 and the joints that score > 0, opaque, rows in ascending order, box then limbs
@@ -482,7 +497,10 @@ class BaseDetector(object):
         A frame is WRITTEN here, so beyond the stream-order and lifetime rules of pre_process_batch, which hold unchanged: every tensor
         must be a view in which no two indices address one byte (frame_writable: expanded and overlapping views raise), a plane
         tuple's luma bytes must lie apart from its chroma bytes, the same tensor may not be given twice -- and that the frames of one
-        call share no bytes otherwise is the caller's promise.  Host arrays raise: there is no CPU fallback."""
+        call share no bytes otherwise is the caller's promise.  Host arrays raise: there is no CPU fallback.
+        row_ids (CUDA int32 [N, M], e.g. DeepSortTracker.row_ids): a row whose id is >= 0 paints all 36 of its primitives in
+        id_palette[id % P] (1..64 (B, G, R) colours, default TRACK_PALETTE); a row with id < 0 keeps the style's palette.  Without
+        row_ids the call is what it was, bit for bit."""
         given, io = frames, self._io
         images, descs = io.batch_input(frames, layout, color, matrix)
         if descs is None and images:
@@ -492,7 +510,26 @@ class BaseDetector(object):
                           on_host="rows on %s: they must be on the model's GPU; there is no CPU fallback")
         io.check_writable(given, images, color)
         draw_rows(io, descs or [], rows.detach().contiguous(), color, matrix, self.cfg.TEST.VIS_THRESH if vis_thresh is None else vis_thresh,
-                  style)
+                  style, row_ids, id_palette)
+        return given
+
+    def draw_tracks(self, frames, tracks, layout="hwc", color="bgr", matrix="bt601", style=None):
+        """Paint `tracks` onto `frames`, in place, on the device, in the current stream -> `frames`.  What the reference's draw_bboxes
+        draws per track: the box in the track's colour (style.palette[id % P]), a filled bar of that colour at the box's top-left
+        corner and the label style.prefix + str(id) on the bar, in this project's own 5 x 7 font (characters 0-9 A-Z space # - . : _,
+        lower case folded; a longer label than 16 characters or any other character: ValueError).  Items in the given order, box then
+        bar then text, the last painted wins; integer-only and bit-exact between the device, the host painter
+        cp_draw_tracks_frames_host and a NumPy restatement (csrc/draw_text_arith.h).
+        frames: as for draw_results, with the same rules for writable frames; host arrays raise.  tracks: per frame an int64 [k, 5]
+        array (x1, y1, x2, y2, track_id), what DeepSortTracker.update returns -- host data, so the item table is built here and goes
+        up with the descriptor table in the call's one upload.  style: a TrackStyle.  One launch, nothing is downloaded."""
+        given, io = frames, self._io
+        images, descs = io.batch_input(frames, layout, color, matrix)
+        if descs is None and images:
+            raise _lib.CenterposeHipError("draw_tracks paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
+                                          "there is no CPU fallback")
+        io.check_writable(given, images, color)
+        draw_track_items(io, descs or [], list(tracks), color, matrix, style)
         return given
 
     def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):

@@ -1,5 +1,7 @@
 """The host side of drawing detections onto device frames: the style record, the palette (and its YUV form) and the launch of the
-painters of csrc/draw_results.hip over an identity descriptor table.  `BaseDetector.draw_results` is the entry point."""
+painters of csrc/draw_results.hip over an identity descriptor table; and of drawing tracks: the track style, the identity palette, the
+item table of boxes and labels and the launch of csrc/draw_tracks.hip.  `BaseDetector.draw_results` / `draw_tracks` are the entry
+points."""
 import ctypes
 
 import numpy as np
@@ -79,14 +81,38 @@ def palette_to_yuv(colors, matrix="bt601"):
     return out
 
 
-def draw_rows(io, frames, rows, color, matrix, vis_thresh, style):
+def _id_palette_struct(colors, matrix):
+    """One DRAW_ID_PALETTE record of 1..64 (B, G, R) colours; `matrix`: as (Y, U, V) for YUV frames."""
+    colors = [tuple(int(v) for v in c) for c in colors]
+    if not 1 <= len(colors) <= 64:
+        raise _lib.CenterposeHipError("an identity palette has 1..64 colours (got %d)" % len(colors))
+    for c in colors:
+        if len(c) != 3 or any(not (0 <= v <= 255) for v in c):
+            raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
+    rec = np.zeros(1, DRAW_ID_PALETTE)
+    rec["count"] = len(colors)
+    rec["colors"][0, :len(colors), :3] = np.asarray(colors if matrix is None else palette_to_yuv(colors, matrix), np.uint8)
+    return rec
+
+
+def draw_rows(io, frames, rows, color, matrix, vis_thresh, style, row_ids=None, id_palette=None):
     """cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8 for checked frames (`io.frame` / `io.yuv_frame` per image) and device rows
-    [N,M,56]: one table upload through `io` (a FrameIO), two launches in the current stream."""
+    [N,M,56]: one table upload through `io` (a FrameIO), two launches in the current stream.  row_ids (CUDA int32 [N,M]): the
+    cp_draw_rows_ids_* forms -- a row whose id is >= 0 is painted in id_palette[id % P] (default: TRACK_PALETTE)."""
     yuv = color in YUV_COLORS
     style = DrawStyle() if style is None else style
     if not isinstance(style, DrawStyle):
         raise _lib.CenterposeHipError("style is a DrawStyle (got %s)" % type(style).__name__)
     N, M = len(frames), int(rows.shape[1])
+    if row_ids is None and id_palette is not None:
+        raise _lib.CenterposeHipError("id_palette= colours the rows named by row_ids=, which is missing")
+    if row_ids is not None:
+        if not isinstance(row_ids, torch.Tensor) or not row_ids.is_cuda or row_ids.device != rows.device:
+            raise _lib.CenterposeHipError("row_ids must be a CUDA int32 tensor [N, M] on the rows' device: there is no CPU fallback")
+        if row_ids.dtype != torch.int32 or tuple(row_ids.shape) != (N, M):
+            raise _lib.CenterposeHipError("row_ids must be int32 [%d, %d] (got %s %s)" % (N, M, row_ids.dtype, tuple(row_ids.shape)))
+        row_ids = row_ids.detach().contiguous()
+        idp = _id_palette_struct(TRACK_PALETTE if id_palette is None else id_palette, matrix if yuv else None)
     if N == 0 or M == 0:
         return
     table = identity_table(frames, yuv)
@@ -96,8 +122,120 @@ def draw_rows(io, frames, rows, color, matrix, vis_thresh, style):
     nbytes = int(L.cp_draw_scratch_bytes(N, M))
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=rows.device)
     table_dev, = io.upload_table([table])
-    fn = L.cp_draw_rows_yuv_frames_u8 if yuv else L.cp_draw_rows_frames_u8
-    rc = fn(ctypes.c_void_p(table_dev.data_ptr()), table.ctypes.data_as(ctypes.c_void_p), N, ctypes.c_void_p(rows.data_ptr()), M,
-            ctypes.c_float(float(vis_thresh)), rec.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(scratch.data_ptr()),
-            ctypes.c_size_t(nbytes), _lib.stream())
-    _lib.check(rc, "cp_draw_rows_yuv_frames_u8" if yuv else "cp_draw_rows_frames_u8")
+    vp = ctypes.c_void_p
+    head = (vp(table_dev.data_ptr()), table.ctypes.data_as(vp), N, vp(rows.data_ptr()), M, ctypes.c_float(float(vis_thresh)),
+            rec.ctypes.data_as(vp), vp(scratch.data_ptr()), ctypes.c_size_t(nbytes))
+    if row_ids is None:
+        name = "cp_draw_rows_yuv_frames_u8" if yuv else "cp_draw_rows_frames_u8"
+        rc = getattr(L, name)(*head, _lib.stream())
+    else:
+        name = "cp_draw_rows_ids_yuv_frames_u8" if yuv else "cp_draw_rows_ids_frames_u8"
+        rc = getattr(L, name)(*head, vp(row_ids.data_ptr()), idp.ctypes.data_as(vp), _lib.stream())
+    _lib.check(rc, name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- tracks: boxes and labels
+# cp_draw_track_item / cp_draw_id_palette (include/centerpose_hip.h)
+TRACK_ITEM = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("color", "u1", (4,)), ("text_color", "u1", (4,)),
+                       ("nchars", "<i4"), ("glyph", "u1", (16,))])
+DRAW_ID_PALETTE = np.dtype([("count", "<i4"), ("colors", "u1", (64, 4))])
+# the label font's characters in glyph order (csrc/draw_text_arith.h); lower case is folded to upper case
+CHARSET = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ #-.:_"
+MAX_LABEL = 16
+
+
+def _wheel():
+    """24 (B, G, R) colours: the hue circle in steps of 15 degrees at full saturation, every second hue darker, listed so that
+    neighbours in the list lie 105 degrees apart.  Integer arithmetic throughout."""
+    out = []
+    for i in range(24):
+        j = (i * 7) % 24
+        h, v = 15 * j, (255, 170)[j % 2]
+        up, down = v * (h % 60) // 60, v * (60 - h % 60) // 60
+        r, g, b = ((v, up, 0), (down, v, 0), (0, v, up), (0, down, v), (up, 0, v), (v, 0, down))[h // 60]
+        out.append((b, g, r))
+    return out
+
+
+# this project's identity colours, (B, G, R): colour of track id i is TRACK_PALETTE[i % 24]
+TRACK_PALETTE = _wheel()
+
+
+def label_glyphs(text):
+    """The glyph indices of a label: at most 16 characters of CHARSET, lower case folded.  ValueError otherwise."""
+    text = str(text).upper()
+    if len(text) > MAX_LABEL:
+        raise ValueError("the label %r has %d characters, at most %d are drawn" % (text, len(text), MAX_LABEL))
+    for ch in text:
+        if ch not in CHARSET:
+            raise ValueError("the label %r holds %r, which the font does not have: its characters are %r" % (text, ch, CHARSET))
+    return [CHARSET.index(ch) for ch in text]
+
+
+class TrackStyle:
+    """How draw_tracks paints: box_thickness 0..64 (0: no box), font_scale 0..8 (pixels per font cell; 0: no bar and no label), the
+    label `prefix` + str(track id), the text colour and the identity palette (1..64 (B, G, R) colours; a track's colour is
+    palette[id % len(palette)], default TRACK_PALETTE)."""
+
+    def __init__(self, box_thickness=3, font_scale=2, prefix="ID ", text_color=(255, 255, 255), palette=None):
+        self.box_thickness, self.font_scale, self.prefix = int(box_thickness), int(font_scale), str(prefix)
+        self.text_color = tuple(int(v) for v in text_color)
+        self.palette = [tuple(int(v) for v in c) for c in (TRACK_PALETTE if palette is None else palette)]
+        if not 0 <= self.box_thickness <= 64:
+            raise _lib.CenterposeHipError("box_thickness %d outside 0..64" % self.box_thickness)
+        if not 0 <= self.font_scale <= 8:
+            raise _lib.CenterposeHipError("font_scale %d outside 0..8" % self.font_scale)
+        if not 1 <= len(self.palette) <= 64:
+            raise _lib.CenterposeHipError("an identity palette has 1..64 colours (got %d)" % len(self.palette))
+        for c in self.palette + [self.text_color]:
+            if len(c) != 3 or any(not (0 <= v <= 255) for v in c):
+                raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
+        label_glyphs(self.prefix)                              # a prefix the font cannot write raises here, not at the first frame
+
+
+def track_items(tracks, style, matrix=None):
+    """The item table of one draw_tracks call: tracks (per frame an integer array [k, 5] of (x1, y1, x2, y2, track_id), what
+    DeepSortTracker.update returns) -> (TRACK_ITEM [N, Kmax], counts int32 [N]).  Coordinates are clamped to [-16384, 16383] and the
+    corners sorted; `matrix`: colours as (Y, U, V)."""
+    tracks = [np.asarray(t).reshape(-1, 5) for t in tracks]
+    for t in tracks:
+        if t.dtype.kind not in "iu":
+            raise _lib.CenterposeHipError("tracks are integer arrays [k, 5] of (x1, y1, x2, y2, track_id), got dtype %s" % t.dtype)
+    N, Kmax = len(tracks), max([len(t) for t in tracks] + [0])
+    items, counts = np.zeros((N, Kmax), TRACK_ITEM), np.array([len(t) for t in tracks], np.int32)
+    conv = (lambda c: c) if matrix is None else (lambda c: palette_to_yuv([c], matrix)[0])
+    text = conv(style.text_color)
+    for n, t in enumerate(tracks):
+        for k, (x1, y1, x2, y2, tid) in enumerate(t.tolist()):
+            glyphs = label_glyphs(style.prefix + str(tid))
+            xa, ya, xb, yb = (min(max(int(v), -16384), 16383) for v in (x1, y1, x2, y2))
+            it = items[n, k]
+            it["x0"], it["y0"], it["x1"], it["y1"] = min(xa, xb), min(ya, yb), max(xa, xb), max(ya, yb)
+            it["color"][:3] = conv(style.palette[tid % len(style.palette)])
+            it["text_color"][:3] = text
+            it["nchars"] = len(glyphs)
+            it["glyph"][:len(glyphs)] = glyphs
+    return items, counts
+
+
+def draw_track_items(io, frames, tracks, color, matrix, style):
+    """cp_draw_tracks_frames_u8 / cp_draw_tracks_yuv_frames_u8 for checked frames and the host `tracks` of those frames: the descriptor
+    table, the items and their counts go up in ONE upload through `io`, one launch in the current stream."""
+    yuv = color in YUV_COLORS
+    style = TrackStyle() if style is None else style
+    if not isinstance(style, TrackStyle):
+        raise _lib.CenterposeHipError("style is a TrackStyle (got %s)" % type(style).__name__)
+    if len(tracks) != len(frames):
+        raise _lib.CenterposeHipError("tracks hold %d arrays for %d frames" % (len(tracks), len(frames)))
+    items, counts = track_items(tracks, style, matrix if yuv else None)
+    N, Kmax = items.shape
+    if N == 0 or int(counts.sum()) == 0:
+        return
+    table = identity_table(frames, yuv)
+    table_dev, items_dev, counts_dev = io.upload_table([table, items, counts])
+    vp = ctypes.c_void_p
+    name = "cp_draw_tracks_yuv_frames_u8" if yuv else "cp_draw_tracks_frames_u8"
+    rc = getattr(_lib.lib(), name)(vp(table_dev.data_ptr()), table.ctypes.data_as(vp), N, vp(items_dev.data_ptr()), items.ctypes.data_as(vp),
+                                   vp(counts_dev.data_ptr()), counts.ctypes.data_as(vp), Kmax, style.box_thickness, style.font_scale,
+                                   _lib.stream())
+    _lib.check(rc, name)

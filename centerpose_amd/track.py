@@ -329,3 +329,31 @@ class DeepSortTracker:
                 _lib.check(L.cp_track_append_f32(vp(self.gallery.data_ptr()), vp(self.ginv.data_ptr()), vp(features.data_ptr()),
                                                  vp(table_dev.data_ptr()), len(table), self.budget, _lib.stream()), "cp_track_append_f32")
         return outs
+
+    def row_ids(self, result, M):
+        """The identities of the last `update`, per detection row -> CUDA int32 [streams, M]: the id of the track matched to row (n, m),
+        -1 everywhere else (a detection that started a track is not a match: `assignments`' rule).  result: the ReidResult given to that
+        update, M: its rows per frame.  `assignments` goes up as one small table, cp_track_row_ids fills and scatters in the current
+        stream: nothing is downloaded and nothing synchronises."""
+        if self.device is None:
+            raise _lib.CenterposeHipError("this tracker was built without a device (device=None): row_ids needs the GPU")
+        if not isinstance(result, ReidResult):
+            raise ValueError("result must be the ReidResult of the last update (got %s)" % type(result).__name__)
+        slots, M = result.slots, int(M)
+        if not isinstance(slots, torch.Tensor) or not slots.is_cuda or slots.device != self.device:
+            raise _lib.CenterposeHipError("result.slots must be a CUDA tensor on %s; there is no CPU fallback" % self.device)
+        if slots.dtype != torch.int32 or tuple(slots.shape) != (self.capacity,):
+            raise ValueError("result.slots must be int32 [%d] (got %s %s)" % (self.capacity, slots.dtype, tuple(slots.shape)))
+        if M < 0 or self.streams * M > 1 << 24:
+            raise ValueError("%d x %d rows are too many for one call (at most 2^24)" % (self.streams, M))
+        ids = self.assignments.astype(np.int32)
+        if not np.array_equal(ids, self.assignments):
+            raise ValueError("a track id does not fit 32 bits")
+        slots = slots.detach().contiguous()
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.streams, M), dtype=torch.int32, device=self.device)
+            ids_dev, = self._io.upload_table([ids])
+            vp = ctypes.c_void_p
+            _lib.check(_lib.lib().cp_track_row_ids(vp(slots.data_ptr()), vp(ids_dev.data_ptr()), self.capacity, self.streams, self.q, M,
+                                                   vp(out.data_ptr()), _lib.stream()), "cp_track_row_ids")
+        return out

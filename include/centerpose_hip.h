@@ -492,6 +492,69 @@ int cp_draw_rows_yuv_frames_u8(const void* table, const void* table_host, int N,
 int cp_draw_rows_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
 int cp_draw_rows_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style);
 
+/* ---- poses in identity colours: the same painters with one colour per tracked row (draw_results(row_ids=) / run_batch(draw="tracks"))
+ * cp_draw_rows_ids_*: exactly the entry point of the same name without `_ids` -- same launches, same checks, same coverage and painter's
+ *   order -- with two more arguments: row_ids DEVICE (HOST for the *_host forms) int [N,M] and id_palette HOST cp_draw_id_palette.  A
+ *   row whose id is >= 0 stores colors[id % count] for all 36 of its primitives; a row with id < 0 keeps the style's palette.  For
+ *   cp_yuv_frame_desc frames the colours are (Y, U, V).  Also checked: both non-null, count in 1..64.  cp_last_kernel():
+ *   draw_raster_kernel<bgr,ids|yuv,ids>.  With every id < 0 the result equals the plain entry point's byte for byte. */
+typedef struct cp_draw_id_palette {     /* 260 bytes */
+    int count;
+    unsigned char colors[64][4];
+} cp_draw_id_palette;
+int cp_draw_rows_ids_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                               const void* style, void* scratch, size_t scratch_bytes, const int* row_ids, const void* id_palette,
+                               void* stream);
+int cp_draw_rows_ids_yuv_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                                   const void* style, void* scratch, size_t scratch_bytes, const int* row_ids, const void* id_palette,
+                                   void* stream);
+int cp_draw_rows_ids_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                 const int* row_ids, const void* id_palette);
+int cp_draw_rows_ids_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                     const int* row_ids, const void* id_palette);
+
+/* ---- draw tracks onto device frames, in place: box, label bar, label (draw_tracks / run_batch(draw="tracks")) --------------------------
+ * What the reference's draw_bboxes puts on the picture per track, by this library's own integer rule (csrc/draw_text_arith.h) and its
+ * own 5 x 7 font.  Frame n paints items[n][0 .. counts[n] - 1] of items[N][Kmax].  With box thickness T (0..64), font scale s (0..8,
+ * 0: no bar and no text), tw = 6 s nchars - s, th = 7 s, an item has three primitives in paint order (paint index item * 3 + primitive):
+ *   0 the box : corners (x0, y0) <= (x1, y1); inside the closed rectangle and x - x0 < T or x1 - x < T or y - y0 < T or y1 - y < T
+ *   1 the bar : the closed rectangle [x0, x0 + tw + 3] x [y0, y0 + th + 4]; absent when nchars = 0 or s = 0
+ *   2 the text: dx = x - (x0 + 2), dy = y - (y0 + 2); 0 <= dx < tw, 0 <= dy < th, u = (dx mod 6s) / s < 5 and bit (4 - u) of row dy / s
+ *               of glyph[dx / 6s] set (bit 4: the leftmost column); absent with the bar
+ *   order: items ascending, primitives in paint order, the last one that covers a pixel gives its colour -- color for box and bar,
+ *   text_color for the text.  Opaque; a frame is never read; uncovered bytes are not written; what leaves the frame is clipped.
+ *   YUV frames: colours are (Y, U, V); luma per covered pixel, chroma sample (i, j) as for cp_draw_rows_yuv_frames_u8.
+ * cp_draw_track_item: corners sorted and in [-16384, 16383]; glyph: indices into the font -- 0..9 the digits, 10..35 A..Z, 36 space,
+ *   37 '#', 38 '-', 39 '.', 40 ':', 41 '_' -- of which the first nchars (0..16) are read.
+ * cp_draw_glyph_rows: the font.  rows[r], r = 0..6 from the top: bit 4 is the leftmost of five columns.  Returns the glyph index, -1 for
+ *   a character outside the set (lower case included: the caller folds it) or a null `rows`.
+ * cp_draw_tracks_frames_u8 / cp_draw_tracks_yuv_frames_u8: ONE launch on `stream` (draw_tracks_kernel: one block per 16x16 pixel tile --
+ *   32x32 for YUV -- and frame walks the frame's items from the back).  table / items / counts: DEVICE; table_host / items_host /
+ *   counts_host: the same bytes on the HOST, where everything is checked before anything is launched (rc 1, cp_last_error): null
+ *   pointers, 0 <= N <= 65535, Kmax >= 0, N * Kmax <= 2^24, T in 0..64, s in 0..8, 0 <= counts[n] <= Kmax, nchars in 0..16, every read
+ *   glyph index inside the font, sorted corners in range, and per frame what cp_draw_rows_frames_u8 checks.  N = 0, Kmax = 0 or no
+ *   items at all succeeds and launches nothing.  The caller's promises are those of cp_draw_rows_frames_u8.  cp_last_kernel():
+ *   draw_tracks_kernel<bgr|yuv>.
+ * cp_draw_tracks_frames_host / cp_draw_tracks_yuv_frames_host: HOST only -- sequential painters over descriptors holding host addresses,
+ *   built from the same statements; same checks.  What the device result is pinned to, byte for byte. */
+typedef struct cp_draw_track_item {     /* 44 bytes */
+    int x0, y0, x1, y1;
+    unsigned char color[4];
+    unsigned char text_color[4];
+    int nchars;
+    unsigned char glyph[16];
+} cp_draw_track_item;
+int cp_sizeof_draw_track_item(void);
+int cp_draw_glyph_rows(int ch, unsigned char* rows);
+int cp_draw_tracks_frames_u8(const void* table, const void* table_host, int N, const void* items, const void* items_host, const int* counts,
+                             const int* counts_host, int Kmax, int box_thickness, int font_scale, void* stream);
+int cp_draw_tracks_yuv_frames_u8(const void* table, const void* table_host, int N, const void* items, const void* items_host,
+                                 const int* counts, const int* counts_host, int Kmax, int box_thickness, int font_scale, void* stream);
+int cp_draw_tracks_frames_host(const void* table_host, int N, const void* items, const int* counts, int Kmax, int box_thickness,
+                               int font_scale);
+int cp_draw_tracks_yuv_frames_host(const void* table_host, int N, const void* items, const int* counts, int Kmax, int box_thickness,
+                                   int font_scale);
+
 /* ---- re-id crops: detections cut out of device frames into the re-id plan's input (reid.ReidExtractor / run_batch(embed=)) -------------
  * What DeepSort._get_features + Extractor._preprocess do per box on the host (demo/tracking/deep_sort.py:66-86,
  * feature_extractor.py:15-39), for every row of rows[N,M,56] and its own frame n, in two launches.  The values are this library's own
@@ -572,6 +635,14 @@ int cp_track_cost_host(const float* gallery, const float* ginv, const int* glen,
                        int M, int S, int Tcap, int budget, int q, float* out);
 int cp_track_append_host(float* gallery, float* ginv, const float* features, const int* table, int n, int budget);
 int cp_linear_assignment_host(const double* cost, int rows, int cols, int ld, int* row_to_col);
+/* cp_track_row_ids: the track ids of the detection slots, per row.  slots DEVICE int [capacity] as above, slot_ids DEVICE int [S * q]
+ *   (the id of the track matched to each detection slot, -1: none), row_ids DEVICE int [S, M]: every entry becomes -1, then
+ *   row_ids[slots[i]] = slot_ids[i] for every i < S * q with slots[i] >= 0 and slot_ids[i] >= 0.  Two launches on `stream` (fill, then
+ *   scatter), no synchronisation.  Slots address distinct rows; a slot outside [0, S * M) is skipped on the device and refused by the
+ *   host twin.  Checked before anything is launched: null pointers, S in 1..65535, q >= 1, M >= 0, capacity >= S * q, S * q and
+ *   S * M <= 2^24.  S * M = 0 succeeds and launches nothing.  cp_track_row_ids_host: HOST only, the sequential twin. */
+int cp_track_row_ids(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids, void* stream);
+int cp_track_row_ids_host(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids);
 
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
