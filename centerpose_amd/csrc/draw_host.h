@@ -116,6 +116,7 @@ inline int dr_check_yuv_frames(const char* who, const DrYuvFrameDesc* t, int N, 
 {
     for (int n = 0; n < N; ++n) {
         const DrYuvFrameDesc& d = t[n];
+        DR_CHECK(d.pad == 0, "%s: frame %d: format word pad = %d: only 8-bit 4:2:0 frames (pad 0) can be drawn on", who, n, d.pad);
         DR_CHECK(d.y_base && d.u_base && d.v_base, "%s: frame %d: null base address (y %p, u %p, v %p)", who, n, (const void*)d.y_base,
                  (const void*)d.u_base, (const void*)d.v_base);
         DR_CHECK(d.H >= 1 && d.H <= DA_MAX_SIDE && d.W >= 1 && d.W <= DA_MAX_SIDE, "%s: frame %d: bad size %d x %d (1..%d)", who, n, d.H,

@@ -1,7 +1,7 @@
 // The 8-bit fixed-point arithmetic of the batched pre-process, once: cv2.resize (INTER_LINEAR) and cv2.warpAffine + normalise per
 // destination pixel, statement for statement those of prepost.hip (resize_u8_kernel, preprocess_kernel).  batch_stages.hip reads its
 // sources from one packed staging buffer (BsPacked), frame_sources.hip reads every frame in place through a pointer and strides
-// (BsStrided), yuv_frames.hip converts (Y, U, V) samples to the three bytes where the taps are loaded (YfSource); the statements
+// (BsStrided), yuv_frames.hip converts (Y, U, V) samples to the three bytes where the taps are loaded (YsSource, yuv_source.h); the statements
 // between the loads are the same functions, so all are bit-identical to the per-image calls.  Include from a translation unit
 // compiled with -ffp-contract=off.
 #pragma once

@@ -5,7 +5,9 @@
 //
 //   cp_reid_select_rows           : which rows get an embedding and in which slot (one wave per frame, ballot + prefix count)
 //   cp_reid_crop_frames_f32       : frames addressed by cp_frame_desc (packed / planar BGR or RGB, 3 or 4 channels, any strides)
-//   cp_reid_crop_yuv_frames_f32   : frames addressed by cp_yuv_frame_desc (NV12 / NV21 / I420), converted per source pixel
+//   cp_reid_crop_yuv_frames_f32   : frames addressed by cp_yuv_frame_desc (NV12 / NV21 / I420), converted per source pixel; a table with
+//                                   any non-zero format word (yuv_source.h: P010 / P016, 4:2:2, 4:4:4, grey) runs the general
+//                                   instantiation, reid_crop_kernel<surfaces>
 //   cp_reid_*_host                : the sequential HOST twins of reid_host.h, same statements
 //
 // The crop kernel is a gather: blockIdx.y is the slot, a thread owns one output pixel, consecutive lanes consecutive ox, so a wave
@@ -50,8 +52,8 @@ __global__ __launch_bounds__(CP_WAVE) void reid_select_kernel(const typename RcD
     if (lane == 0) counts[n] = count;
 }
 
-// grid (128 * 64 / 256, cap)
-template <bool YUV>
+// grid (128 * 64 / 256, cap).  GEN (YUV only): the sampler reads the frame's format word; false: every frame is 8-bit 4:2:0
+template <bool YUV, bool GEN>
 __global__ __launch_bounds__(RC_THREADS) void reid_crop_kernel(const typename RcDesc<YUV>::type* __restrict__ table, int N,
                                                                const float* __restrict__ rows, int M, float vis_thresh,
                                                                const int* __restrict__ slots, YfCoef coef, RaNorm nm, float* __restrict__ out)
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(RC_THREADS) void reid_crop_kernel(const typename Rc
     if (idx >= 0 && idx < N * M && ra_select(rows + (size_t)idx * RA_ROW, vis_thresh, table[idx / M].H, table[idx / M].W, &b)) {
         const typename RcDesc<YUV>::type& d = table[idx / M];
         if constexpr (YUV)
-            ra_pixel(rh_yuv_source(d, coef), b, oy, ox, nm, r);
+            ra_pixel(rh_yuv_source<GEN>(d, coef), b, oy, ox, nm, r);
         else
             ra_pixel(rh_source(d), b, oy, ox, nm, r);
     }
@@ -122,6 +124,7 @@ extern "C" int cp_reid_select_rows(const void* table, const void* table_host, in
         const int W = yuv ? ((const RhYuvFrameDesc*)table_host)[n].W : ((const RhFrameDesc*)table_host)[n].W;
         CP_CHECK_ARG(H > 0 && W > 0 && (long long)H * W < (1ll << 29), "%s: frame %d: bad size %d x %d", who, n, H, W);
     }
+    if (yuv) RC_FORWARD(rh_check_yuv_words(who, (const RhYuvFrameDesc*)table_host, N, err, errn));
     if (yuv)
         hipLaunchKernelGGL(reid_select_kernel<true>, dim3((unsigned)N), dim3(CP_WAVE), 0, (hipStream_t)stream, (const RhYuvFrameDesc*)table, N,
                            rows, M, vis_thresh, cap, slots, counts);
@@ -142,17 +145,24 @@ static int rc_launch(const char* who, const void* table, const void* table_host,
     RC_FORWARD(rh_check_norm(who, nm, err, errn));
     CP_CHECK_ARG(table && table_host && slots && out && (rows || M == 0), "%s: null pointer", who);
     YfCoef k = {0, 0, 0, 0, 0, 0};
+    bool general = false;
     if constexpr (YUV) {
         RC_FORWARD(rh_check_yuv_frames(who, (const Desc*)table_host, N, coef, err, errn));
         k = YfCoef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+        for (int n = 0; n < N; ++n) general = general || ((const Desc*)table_host)[n].pad != 0;
     } else {
         RC_FORWARD(rh_check_frames(who, (const Desc*)table_host, N, err, errn));
     }
     static_assert((RA_OUT_H * RA_OUT_W) % RC_THREADS == 0, "the crop grid is exact");
-    hipLaunchKernelGGL(reid_crop_kernel<YUV>, dim3(RA_OUT_H * RA_OUT_W / RC_THREADS, (unsigned)cap), dim3(RC_THREADS), 0, (hipStream_t)stream,
-                       (const Desc*)table, N, rows, M, vis_thresh, slots, k, *nm, out);
+    const dim3 grid(RA_OUT_H * RA_OUT_W / RC_THREADS, (unsigned)cap);
+    if (general)
+        hipLaunchKernelGGL((reid_crop_kernel<YUV, YUV>), grid, dim3(RC_THREADS), 0, (hipStream_t)stream, (const Desc*)table, N, rows, M, vis_thresh,
+                           slots, k, *nm, out);
+    else
+        hipLaunchKernelGGL((reid_crop_kernel<YUV, false>), grid, dim3(RC_THREADS), 0, (hipStream_t)stream, (const Desc*)table, N, rows, M, vis_thresh,
+                           slots, k, *nm, out);
     CP_CHECK_LAUNCH("reid_crop_kernel");
-    cp_note_kernel(YUV ? "reid_crop_kernel<yuv>" : "reid_crop_kernel<bgr>");
+    cp_note_kernel(general ? "reid_crop_kernel<surfaces>" : YUV ? "reid_crop_kernel<yuv>" : "reid_crop_kernel<bgr>");
     return 0;
 }
 

@@ -7,11 +7,11 @@
 #include <stddef.h>
 #include <stdio.h>
 #include "reid_arith.h"
-#if !defined(__HIPCC__)     // yuv_arith.h marks its functions for both sides; a host compiler knows neither word
+#if !defined(__HIPCC__)     // yuv_arith.h (under yuv_source.h) marks its functions for both sides; a host compiler knows neither word
 #define __host__
 #define __device__
 #endif
-#include "yuv_arith.h"
+#include "yuv_source.h"
 
 // mirror of cp_frame_desc (include/centerpose_hip.h); the crops read base, the strides, ch_off, H and W
 struct RhFrameDesc {
@@ -57,21 +57,12 @@ RA_HD RhStrided rh_source(const RhFrameDesc& d)
     return s;
 }
 
-// the same from 4:2:0 planes: nearest chroma, yuv_arith.h per source pixel, exactly as the pre-process converts its taps
-struct RhYuv {
-    const unsigned char *y, *u, *v;
-    long long y_row, y_pix, c_row, c_pix;
-    YfCoef k;
-    RA_HD void load(int r, int c, int out[3]) const
-    {
-        const long long ci = (long long)(r >> 1) * c_row + (long long)(c >> 1) * c_pix;
-        yf_yuv_to_bgr(y[(long long)r * y_row + (long long)c * y_pix], u[ci], v[ci], k, out);
-    }
-};
-RA_HD RhYuv rh_yuv_source(const RhYuvFrameDesc& d, const YfCoef& k)
+// the same from YUV planes: yuv_source.h's sampler (nearest chroma, yuv_arith.h per source pixel, exactly as the pre-process converts its
+// taps).  GENERAL = false: 8-bit 4:2:0, every frame of the call has format word 0; true: any format word.
+template <bool GENERAL>
+RA_HD YsSource<GENERAL> rh_yuv_source(const RhYuvFrameDesc& d, const YfCoef& k)
 {
-    RhYuv s = {d.y_base, d.u_base, d.v_base, d.y_row, d.y_pix, d.c_row, d.c_pix, k};
-    return s;
+    return ys_source<GENERAL>(d, k);
 }
 
 #define RH_CHECK(cond, ...)                      \
@@ -124,13 +115,20 @@ inline int rh_check_yuv_frames(const char* who, const RhYuvFrameDesc* t, int N, 
     RH_CHECK(yf_coef_fits(coef, &why), "%s: bad conversion matrix: %s", who, why);
     for (int n = 0; n < N; ++n) {
         const RhYuvFrameDesc& d = t[n];
-        RH_CHECK(d.y_base && d.u_base && d.v_base, "%s: frame %d: null base address (y %p, u %p, v %p)", who, n, (const void*)d.y_base,
-                 (const void*)d.u_base, (const void*)d.v_base);
         RH_CHECK(d.H > 0 && d.W > 0 && (long long)d.H * d.W < (1ll << 29), "%s: frame %d: bad size %d x %d", who, n, d.H, d.W);
-        RH_CHECK(d.y_row >= 0 && d.y_pix >= 0 && d.c_row >= 0 && d.c_pix >= 0, "%s: frame %d: negative stride", who, n);
-        const __int128 y_last = (__int128)(d.H - 1) * d.y_row + (__int128)(d.W - 1) * d.y_pix;
-        const __int128 c_last = (__int128)((d.H - 1) >> 1) * d.c_row + (__int128)((d.W - 1) >> 1) * d.c_pix;
-        RH_CHECK(y_last < ((__int128)1 << 62) && c_last < ((__int128)1 << 62), "%s: frame %d: strides address more than 2^62 bytes", who, n);
+        const char* bad = ys_check_format(d);
+        RH_CHECK(!bad, "%s: frame %d: %s (format word pad = %d; y %p, u %p, v %p)", who, n, bad, d.pad, (const void*)d.y_base,
+                 (const void*)d.u_base, (const void*)d.v_base);
+    }
+    return 0;
+}
+
+// the selection reads H and W only; of a YUV table it also refuses format words no crop would take
+inline int rh_check_yuv_words(const char* who, const RhYuvFrameDesc* t, int N, char* err, size_t errn)
+{
+    for (int n = 0; n < N; ++n) {
+        const char* bad = ys_check_word(t[n].pad);
+        RH_CHECK(!bad, "%s: frame %d: format word pad = %d: %s", who, n, t[n].pad, bad);
     }
     return 0;
 }
@@ -184,9 +182,10 @@ inline int rh_select_host(const void* table, int yuv, int N, const float* rows, 
     const char* who = "reid_select_rows_host";
     if (int rc = rh_check_call(who, N, M, cap, err, errn)) return rc;
     RH_CHECK(table && slots && counts && (rows || M == 0), "%s: null pointer", who);
-    if (yuv)
+    if (yuv) {
+        if (int rc = rh_check_yuv_words(who, (const RhYuvFrameDesc*)table, N, err, errn)) return rc;
         rh_select((const RhYuvFrameDesc*)table, N, rows, M, vis_thresh, cap, slots, counts);
-    else
+    } else
         rh_select((const RhFrameDesc*)table, N, rows, M, vis_thresh, cap, slots, counts);
     return 0;
 }
@@ -212,6 +211,6 @@ inline int rh_crop_yuv_frames_host(const RhYuvFrameDesc* table, int N, const int
     RH_CHECK(table && slots && out && (rows || M == 0), "%s: null pointer", who);
     if (int rc = rh_check_yuv_frames(who, table, N, coef, err, errn)) return rc;
     const YfCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
-    rh_crop(table, N, rows, M, vis_thresh, slots, cap, *nm, out, [&](const RhYuvFrameDesc& d) { return rh_yuv_source(d, k); });
+    rh_crop(table, N, rows, M, vis_thresh, slots, cap, *nm, out, [&](const RhYuvFrameDesc& d) { return rh_yuv_source<true>(d, k); });
     return 0;
 }

@@ -13,10 +13,14 @@
 // conversion is yuv_arith.h's (integer, per source pixel, before the resize and before the warp); everything after the load is
 // pre_arith.h's, shared with batch_stages.hip and frame_sources.hip: results are bit-identical to cp_preprocess_frames_u8_f32 on the
 // packed BGR image obtained by converting every pixel.  Compiled with -ffp-contract=off, like frame_sources.hip.
+//
+// That is format word 0 of a descriptor.  Any other word (yuv_source.h: 4:2:2 / 4:4:4 chroma, 16-bit samples as in P010 / P016, grey)
+// sends the whole launch through the general instantiations, reported as preprocess_yuv_surfaces_kernel<vec4|scalar>; the conversion
+// of 16-bit samples is yf_yuv16_to_bgr, on the CPU through cp_yuv16_to_bgr_host.
 #include <cmath>
 #include "common.h"
 #include "pre_arith.h"
-#include "yuv_arith.h"
+#include "yuv_source.h"
 
 // mirror of cp_yuv_frame_desc (include/centerpose_hip.h)
 struct YuvFrameDesc {
@@ -28,31 +32,19 @@ struct YuvFrameDesc {
     long long mid_off;      // byte offset of the resized uint8 [NH,NW,3] BGR image in the scratch buffer, < 0: (NH,NW) == (H,W), no resize
     int H, W, NH, NW;
     double mi[6];           // INVERTED warp matrix: destination pixel -> coordinates in the (resized) image
-    int slot, pad;          // output batch index of the image (its mirrored twin goes to slot + 1)
+    int slot, pad;          // output batch index of the image (its mirrored twin goes to slot + 1); pad: the format word (yuv_source.h)
 };
 static_assert(sizeof(YuvFrameDesc) == 136, "cp_yuv_frame_desc is 136 bytes");
 
-// A YUV 4:2:0 frame as a source of pre_arith.h: load(y, x, v) converts the samples of pixel (y, x) to its B, G, R bytes.
-// Three byte loads per tap, whatever the plane layout.  Two refinements were measured on the device and are NOT here, because
-// both made the launches slower: one 2-byte load for an interleaved pair at an even address, and keeping a
-// lane's last chroma pairs for the neighbouring taps.
-struct YfSource {
-    const unsigned char *y, *u, *v;
-    long long y_row, y_pix, c_row, c_pix;
-    YfCoef k;
-
-    __device__ __forceinline__ YfSource(const YuvFrameDesc& d, const YfCoef& coef)
-        : y(d.y_base), u(d.u_base), v(d.v_base), y_row(d.y_row), y_pix(d.y_pix), c_row(d.c_row), c_pix(d.c_pix), k(coef) {}
-
-    __device__ __forceinline__ void load(int yy, int xx, int bgr[3]) const
-    {
-        const long long off = (long long)(yy >> 1) * c_row + (long long)(xx >> 1) * c_pix;
-        yf_yuv_to_bgr(y[(long long)yy * y_row + (long long)xx * y_pix], u[off], v[off], k, bgr);
-    }
-};
+// A YUV frame as a source of pre_arith.h is yuv_source.h's YsSource: load(y, x, v) converts the samples of pixel (y, x) to its B, G, R
+// bytes.  GEN = false: 8-bit 4:2:0 (every frame of the launch has format word 0), three byte loads per tap, whatever the plane layout.
+// Two refinements were measured on the device and are NOT there, because both made the launches slower: one
+// 2-byte load for an interleaved pair at an even address, and keeping a lane's last chroma pairs for the neighbouring taps.
+// GEN = true: any format word, read per frame (uniform over a block): 4:2:2 / 4:4:4 / grey, 16-bit samples by one 2-byte load each.
 
 // blockIdx.y: frame; blockIdx.x: grid-stride tiles of its resized pixels.  Frames without a resize leave at once.  The intermediate is
 // packed [NH,NW,3] BGR, whatever the frame's plane layout.
+template <bool GEN>
 __global__ __launch_bounds__(BS_THREADS) void resize_yuv_frames_u8_kernel(unsigned char* __restrict__ scratch, const YuvFrameDesc* __restrict__ table,
                                                                           YfCoef coef)
 {
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(BS_THREADS) void resize_yuv_frames_u8_kernel(unsign
     if (d.mid_off < 0) return;
     const int H = d.H, W = d.W, NH = d.NH, NW = d.NW, total = NH * NW;
     const double scale_x = (double)W / NW, scale_y = (double)H / NH;
-    const YfSource src(d, coef);
+    const YsSource<GEN> src = ys_source<GEN>(d, coef);
     unsigned char* dst = scratch + d.mid_off;
     for (int i = blockIdx.x * BS_THREADS + threadIdx.x; i < total; i += gridDim.x * BS_THREADS) {
         const int dy = i / NW, dx = i - dy * NW;
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(BS_THREADS) void resize_yuv_frames_u8_kernel(unsign
 
 // blockIdx.y: frame; blockIdx.x: grid-stride tiles of its OH x OW destination pixels (bs_warp_image, pre_arith.h).  The source is the
 // frame itself, converted tap by tap (no resize), or its packed BGR intermediate; the choice is uniform over the block.
-template <bool VEC>
+template <bool VEC, bool GEN>
 __global__ __launch_bounds__(BS_THREADS) void preprocess_yuv_frames_kernel(const unsigned char* __restrict__ scratch, const YuvFrameDesc* __restrict__ table,
                                                                            YfCoef coef, float* __restrict__ out, int OH, int OW, BsNorm nm, int flip)
 {
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(BS_THREADS) void preprocess_yuv_frames_kernel(const
     const size_t total = (size_t)OH * OW;
     float* o = out + (size_t)d.slot * 3 * total;
     if (d.mid_off < 0) {
-        const YfSource src(d, coef);
+        const YsSource<GEN> src = ys_source<GEN>(d, coef);
         bs_warp_image<VEC>(src, d.NH, d.NW, m, o, o + 3 * total, OH, OW, nm, flip);
     } else {
         const BsPacked src = {scratch + d.mid_off, d.NW};
@@ -115,6 +107,43 @@ extern "C" int cp_yuv_to_bgr_host(const unsigned char* y, const unsigned char* u
     return 0;
 }
 
+// the same for n triples of 16-bit container values, by yf_yuv16_to_bgr
+extern "C" int cp_yuv16_to_bgr_host(const unsigned short* y, const unsigned short* u, const unsigned short* v, size_t n, const int* coef,
+                                    unsigned char* bgr)
+{
+    CP_CHECK_ARG(y && u && v && bgr, "yuv16_to_bgr_host: null pointer");
+    YfCoef k;
+    if (int rc = yf_check_coef(coef, "yuv16_to_bgr_host", &k)) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        int p[3];
+        yf_yuv16_to_bgr(y[i], u[i], v[i], k, p);
+        bgr[3 * i] = (unsigned char)p[0]; bgr[3 * i + 1] = (unsigned char)p[1]; bgr[3 * i + 2] = (unsigned char)p[2];
+    }
+    return 0;
+}
+
+template <bool GEN>
+static int yf_launch(const YuvFrameDesc* table, int N, const YfCoef& k, unsigned char* scratch, long long max_resized, float* out, int OH, int OW,
+                     const BsNorm& nm, int flip, bool vec, hipStream_t s)
+{
+    if (max_resized > 0) {
+        long long gx = (max_resized + BS_THREADS - 1) / BS_THREADS;
+        if (gx > 4096) gx = 4096;
+        hipLaunchKernelGGL(resize_yuv_frames_u8_kernel<GEN>, dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch, table, k);
+        CP_CHECK_LAUNCH(GEN ? "resize_yuv_surfaces_u8_kernel" : "resize_yuv_frames_u8_kernel");
+    }
+    long long gx = ((long long)OH * (vec ? OW / 4 : OW) + BS_THREADS - 1) / BS_THREADS;
+    if (gx > 4096) gx = 4096;
+    if (vec)
+        hipLaunchKernelGGL((preprocess_yuv_frames_kernel<true, GEN>), dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch, table, k, out,
+                           OH, OW, nm, flip ? 1 : 0);
+    else
+        hipLaunchKernelGGL((preprocess_yuv_frames_kernel<false, GEN>), dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch, table, k, out,
+                           OH, OW, nm, flip ? 1 : 0);
+    CP_CHECK_LAUNCH(GEN ? "preprocess_yuv_surfaces_kernel" : "preprocess_yuv_frames_kernel");
+    return 0;
+}
+
 // table / table_host: the same N descriptors on the device and on the host (the host copy is what is checked).  The size of a plane's
 // allocation is not known here: bases and strides must describe memory the caller owns (a tensor's own shape / strides do).
 extern "C" int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* table_host, int N, const int* coef /* host 6 */,
@@ -129,17 +158,15 @@ extern "C" int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* ta
     const YuvFrameDesc* th = (const YuvFrameDesc*)table_host;
     const int nb = flip ? 2 : 1;
     long long max_resized = 0;
+    bool general = false;
     for (int n = 0; n < N; ++n) {
         const YuvFrameDesc& d = th[n];
-        CP_CHECK_ARG(d.y_base && d.u_base && d.v_base, "preprocess_yuv_frames: frame %d: null base address (y %p, u %p, v %p)", n,
-                     (const void*)d.y_base, (const void*)d.u_base, (const void*)d.v_base);
         CP_CHECK_ARG(d.H > 0 && d.W > 0 && d.NH > 0 && d.NW > 0 && (long long)d.H * d.W < (1ll << 29) && (long long)d.NH * d.NW < (1ll << 29),
                      "preprocess_yuv_frames: frame %d: bad size %d x %d -> %d x %d", n, d.H, d.W, d.NH, d.NW);
-        CP_CHECK_ARG(d.y_row >= 0 && d.y_pix >= 0 && d.c_row >= 0 && d.c_pix >= 0, "preprocess_yuv_frames: frame %d: negative stride", n);
-        const __int128 y_last = (__int128)(d.H - 1) * d.y_row + (__int128)(d.W - 1) * d.y_pix;
-        const __int128 c_last = (__int128)((d.H - 1) >> 1) * d.c_row + (__int128)((d.W - 1) >> 1) * d.c_pix;
-        CP_CHECK_ARG(y_last < ((__int128)1 << 62) && c_last < ((__int128)1 << 62),
-                     "preprocess_yuv_frames: frame %d: strides address more than 2^62 bytes", n);
+        const char* bad = ys_check_format(d);
+        CP_CHECK_ARG(!bad, "preprocess_yuv_frames: frame %d: %s (format word pad = %d; y %p, u %p, v %p)", n, bad, d.pad, (const void*)d.y_base,
+                     (const void*)d.u_base, (const void*)d.v_base);
+        general = general || d.pad != 0;
         const long long mid_bytes = (long long)d.NH * d.NW * 3;
         if (d.mid_off >= 0) {
             CP_CHECK_ARG(scratch && d.mid_off + mid_bytes <= (long long)scratch_bytes, "preprocess_yuv_frames: frame %d: resized image lies outside the scratch buffer", n);
@@ -149,25 +176,16 @@ extern "C" int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* ta
         }
         CP_CHECK_ARG(d.slot >= 0 && d.slot + nb <= out_batch, "preprocess_yuv_frames: frame %d: output slot %d outside the batch of %d", n, d.slot, out_batch);
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (max_resized > 0) {
-        long long gx = (max_resized + BS_THREADS - 1) / BS_THREADS;
-        if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(resize_yuv_frames_u8_kernel, dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch, (const YuvFrameDesc*)table, k);
-        CP_CHECK_LAUNCH("resize_yuv_frames_u8_kernel");
-    }
     BsNorm nm;
     for (int c = 0; c < 3; ++c) { nm.mean[c] = mean[c]; nm.sd[c] = std_[c]; }
     const bool vec = OW % 4 == 0 && ((size_t)out & 15) == 0;
-    long long gx = ((long long)OH * (vec ? OW / 4 : OW) + BS_THREADS - 1) / BS_THREADS;
-    if (gx > 4096) gx = 4096;
-    if (vec)
-        hipLaunchKernelGGL(preprocess_yuv_frames_kernel<true>, dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch,
-                           (const YuvFrameDesc*)table, k, out, OH, OW, nm, flip ? 1 : 0);
+    // every frame 8-bit 4:2:0: the kernels as they were before the format word; else ONE general pair for all frames of the launch
+    if (int rc = general ? yf_launch<true>((const YuvFrameDesc*)table, N, k, scratch, max_resized, out, OH, OW, nm, flip, vec, (hipStream_t)stream)
+                         : yf_launch<false>((const YuvFrameDesc*)table, N, k, scratch, max_resized, out, OH, OW, nm, flip, vec, (hipStream_t)stream))
+        return rc;
+    if (general)
+        cp_note_kernel(vec ? "preprocess_yuv_surfaces_kernel<vec4>" : "preprocess_yuv_surfaces_kernel<scalar>");
     else
-        hipLaunchKernelGGL(preprocess_yuv_frames_kernel<false>, dim3((unsigned)gx, (unsigned)N), dim3(BS_THREADS), 0, s, scratch,
-                           (const YuvFrameDesc*)table, k, out, OH, OW, nm, flip ? 1 : 0);
-    CP_CHECK_LAUNCH("preprocess_yuv_frames_kernel");
-    cp_note_kernel(vec ? "preprocess_yuv_frames_kernel<vec4>" : "preprocess_yuv_frames_kernel<scalar>");
+        cp_note_kernel(vec ? "preprocess_yuv_frames_kernel<vec4>" : "preprocess_yuv_frames_kernel<scalar>");
     return 0;
 }

@@ -36,8 +36,9 @@ from .decode import multi_pose_decode
 # frames.py and draw.py hold what used to be defined here: besides what this module uses, the names callers import from it stay
 from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv      # noqa: F401
 from .draw import TRACK_ITEM, TRACK_PALETTE, TrackStyle, draw_track_items                                            # noqa: F401
-from .frames import (FRAME_DESC, PRE_DESC, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO, _check_layout, byte_range,      # noqa: F401
-                     check_rows, frame_geometry, frame_writable, identity_table, yuv_frame_geometry)
+from .frames import (FRAME_DESC, PRE_DESC, SURFACE_COLORS, SURFACE_MATRICES, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO,      # noqa: F401
+                     _check_layout, byte_range, check_drawable, check_rows, frame_geometry, frame_writable, identity_table, is_yuv, yuv_coef,
+                     yuv_frame_geometry, yuv_surface_geometry)
 from .model import create_model, load_model
 from .post_process import get_affine_transform
 
@@ -178,8 +179,8 @@ class BaseDetector(object):
         color "nv12" / "nv21" / "i420": image is one 4:2:0 YUV frame on the device (a tuple of plane tensors or, for nv12 / nv21, one
         surface tensor), converted with `matrix` ("bt601" / "bt709") -- see pre_process_batch."""
         _check_layout(layout, color, matrix)
-        if color in YUV_COLORS or isinstance(image, torch.Tensor):
-            if color not in YUV_COLORS and image.dim() != 3:
+        if is_yuv(color) or isinstance(image, torch.Tensor):
+            if not is_yuv(color) and image.dim() != 3:
                 raise _lib.CenterposeHipError("pre_process takes one 3-D frame tensor, got shape %s (N frames: pre_process_batch)"
                                               % (tuple(image.shape),))
             x, metas = self.pre_process_batch([image], scale, layout, color, matrix)      # (bt601, checked above, unless YUV)
@@ -339,12 +340,16 @@ class BaseDetector(object):
         surface, split into its plane views here.  Any strides; nothing is copied.  cp_preprocess_yuv_frames_u8_f32 converts every
         pixel to BGR where it is loaded, with the limited-range `matrix` "bt601" (cv2's COLOR_YUV2BGR_NV12 arithmetic) or "bt709",
         nearest chroma: bit-identical to the call on the HxWx3 BGR host array that conversion gives (csrc/yuv_arith.h).  The
-        stream-order and lifetime rules above hold for every plane.  Host YUV arrays are not taken."""
+        stream-order and lifetime rules above hold for every plane.  Host YUV arrays are not taken.
+        Further YUV colours (frames.yuv_surface_geometry has the forms): "p010" / "p016" (uint16 or int16 planes or one surface, the
+        samples as stored, MSB aligned), "i422", "i444", "i400" (grey), packed "yuyv" / "uyvy"; further matrices for every YUV colour:
+        "bt601-full", "bt709-full" (JPEG / MJPEG), "bt2020-limited", "bt2020-full" (frames.SURFACE_MATRICES).  Same rules, same
+        bit-identity to the converted BGR array (csrc/yuv_source.h); these colours and matrices are read, never drawn on."""
         io = self._io
         images, frames = io.batch_input(images, layout, color, matrix)
         if not images:
             raise _lib.CenterposeHipError("pre_process_batch needs at least one image")
-        coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+        coef = yuv_coef(matrix) if is_yuv(color) else None
         shapes = [im.shape[0:2] for im in images] if frames is None else [(f.H, f.W) for f in frames]
         offsets, nbytes = self._batch_layout(shapes) if frames is None else (None, 0)
         table, scratch_bytes, inp_h, inp_w, metas = self._pre_table(shapes, offsets, list(range(len(images))), scale, frames, coef is not None)
@@ -380,7 +385,7 @@ class BaseDetector(object):
         they are read in place, the descriptor tables are the call's only upload, and the results equal those of the same frames
         given as host arrays.  The same stream-order and lifetime rules hold.  Frames in 4:2:0 YUV (color "nv12" / "nv21" / "i420",
         `matrix`): a list of plane tuples or surface tensors as for pre_process_batch, the rules per plane; the results equal those of
-        the converted BGR host arrays.
+        the converted BGR host arrays; the further YUV colours and matrices of pre_process_batch go the same way, but raise with `draw`.
         return_device=True (host or device input): the rows as ONE device tensor float32 [N, S*K, 56] in input order instead of the
         list -- no download and no synchronisation; the tensor is ready in the current stream's order.
         draw=True (device frames only): once the rows are in input order the frames are painted with them, in place, as
@@ -401,8 +406,11 @@ class BaseDetector(object):
         with their default styles.  The return value is exactly what it is without `draw`; the painting adds no synchronisation and
         one table upload per painting call."""
         given, io = images, self._io
+        if draw:
+            _check_layout(layout, color, matrix)
+            check_drawable(color, matrix)
         images, frames = io.batch_input(images, layout, color, matrix)
-        coef = YUV_MATRICES[matrix] if color in YUV_COLORS else None
+        coef = yuv_coef(matrix) if is_yuv(color) else None
         if embed is not None:
             if frames is None:
                 raise ValueError("embed= takes its crops from frames on the device (CUDA uint8 tensors): host arrays are not read, "
@@ -491,6 +499,7 @@ class BaseDetector(object):
         frames: as for pre_process_batch -- a list of CUDA uint8 tensors or one 4-D tensor (`layout`, `color`, C = 3 or 4), or with
         color "nv12" / "nv21" / "i420" a list of plane tuples / surface tensors; for those the palette is converted to (Y, U, V) with
         `matrix` (palette_to_yuv), luma is written per pixel and a chroma sample takes the latest-painted colour among its 2x2 pixels.
+        The colours of frames.SURFACE_COLORS and the matrices of frames.SURFACE_MATRICES raise before anything is launched.
         Three bytes per covered pixel: a fourth channel, row padding and everything outside a view keep their bytes.
         rows: CUDA float32 [N, M, 56] in image coordinates, as run_batch(..., return_device=True) returns them ([M, 56]: one frame).
         style: a DrawStyle.  The descriptor table is the only upload; nothing is downloaded and nothing synchronises.
@@ -502,6 +511,8 @@ class BaseDetector(object):
         id_palette[id % P] (1..64 (B, G, R) colours, default TRACK_PALETTE); a row with id < 0 keeps the style's palette.  Without
         row_ids the call is what it was, bit for bit."""
         given, io = frames, self._io
+        _check_layout(layout, color, matrix)
+        check_drawable(color, matrix)
         images, descs = io.batch_input(frames, layout, color, matrix)
         if descs is None and images:
             raise _lib.CenterposeHipError("draw_results paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -524,6 +535,8 @@ class BaseDetector(object):
         array (x1, y1, x2, y2, track_id), what DeepSortTracker.update returns -- host data, so the item table is built here and goes
         up with the descriptor table in the call's one upload.  style: a TrackStyle.  One launch, nothing is downloaded."""
         given, io = frames, self._io
+        _check_layout(layout, color, matrix)
+        check_drawable(color, matrix)
         images, descs = io.batch_input(frames, layout, color, matrix)
         if descs is None and images:
             raise _lib.CenterposeHipError("draw_tracks paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -533,7 +546,7 @@ class BaseDetector(object):
         return given
 
     def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):
-        if isinstance(x, (np.ndarray, torch.Tensor)) or (color in YUV_COLORS and isinstance(x, (tuple, list))):
+        if isinstance(x, (np.ndarray, torch.Tensor)) or (is_yuv(color) and isinstance(x, (tuple, list))):
             return _ArraySource(x, layout, color, matrix)
         if isinstance(x, str):
             return _ArraySource(_imread(x), layout, color, matrix)

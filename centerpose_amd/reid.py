@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, nets
 from .engine import Engine
-from .frames import YUV_COLORS, YUV_MATRICES, FrameIO, check_rows, identity_table
+from .frames import FrameIO, check_rows, identity_table, is_yuv, yuv_coef
 
 # cp_reid_norm (include/centerpose_hip.h)
 REID_NORM = np.dtype([("scale", "<f4"), ("mean", "<f4", (3,)), ("std", "<f4", (3,)), ("rgb", "<i4")])
@@ -89,8 +89,9 @@ class ReidExtractor:
         """Embeddings of the detections `rows` of `frames` -> ReidResult, on the device, in the current stream, no synchronisation;
         the descriptor table is the only upload.
         frames: as for draw_results -- a list of CUDA uint8 tensors or one 4-D tensor (`layout`, `color`, C = 3 or 4), or with color
-        "nv12" / "nv21" / "i420" a list of plane tuples / surface tensors (`matrix`).  They are only read: expanded and overlapping
-        views are fine.  Host arrays raise ValueError: the crops are taken from device frames, there is no CPU fallback.
+        "nv12" / "nv21" / "i420" a list of plane tuples / surface tensors (`matrix`); the further YUV colours and matrices of
+        pre_process_batch ("p010", "i422", "i444", "i400", "yuyv", ...; "bt601-full", ...) are taken too.  They are only read: expanded
+        and overlapping views are fine.  Host arrays raise ValueError: the crops are taken from device frames, there is no CPU fallback.
         rows: CUDA float32 [N, M, 56] in image coordinates, as run_batch(..., return_device=True) returns them ([M, 56]: one frame).
         A row is embedded iff its score is > vis_thresh and its clamped box has pixels (csrc/reid_arith.h); N > capacity raises."""
         if _holds_host_array(frames):
@@ -101,8 +102,8 @@ class ReidExtractor:
         return self._embed(descs or [], rows.detach().contiguous(), color, matrix, vis_thresh)
 
     def _embed(self, descs, rows, color, matrix, vis_thresh):
-        """select + crop + one replay for checked frames (a frames.Frame / YuvFrame per frame) and device rows [N, M, 56]."""
-        yuv = color in YUV_COLORS
+        """select + crop + one replay for checked frames (a frames.Frame / YuvFrame / YuvSurface per frame) and device rows [N, M, 56]."""
+        yuv = is_yuv(color)
         N, M, cap = len(descs), int(rows.shape[1]), self.capacity
         if N < 1:
             raise ValueError("embed needs at least one frame")
@@ -124,7 +125,7 @@ class ReidExtractor:
             x = self.engine.input
             norm = self.norm.ctypes.data_as(vp)
             if yuv:
-                coef = (ctypes.c_int * 6)(*YUV_MATRICES[matrix])
+                coef = (ctypes.c_int * 6)(*yuv_coef(matrix))
                 _lib.check(L.cp_reid_crop_yuv_frames_f32(vp(table_dev.data_ptr()), th, N, coef, vp(rows.data_ptr()), M, thr,
                                                          vp(slots.data_ptr()), cap, norm, vp(x.data_ptr()), _lib.stream()),
                            "cp_reid_crop_yuv_frames_f32")

@@ -427,7 +427,26 @@ int cp_preprocess_frames_u8_f32(const void* table, const void* table_host, int N
  *   strides >= 0, every plane's largest addressed offset below 2^62, mid_off / scratch / slot as for cp_preprocess_frames_u8_f32,
  *   N <= 65535, and coef as above.  The caller vouches for the planes' memory, stream order and lifetime exactly as for cp_frame_desc,
  *   per plane.  cp_last_kernel(): preprocess_yuv_frames_kernel<vec4|scalar>.
- * cp_yuv_to_bgr_host: HOST only -- the conversion of n (Y, U, V) triples to bgr[3 * n] by the same statements the kernels compile. */
+ * cp_yuv_to_bgr_host: HOST only -- the conversion of n (Y, U, V) triples to bgr[3 * n] by the same statements the kernels compile.
+ * Format word: the descriptor's trailing `pad` says what the planes hold (csrc/yuv_source.h); 0 is everything above.
+ *       bit 0  chroma not subsampled horizontally        bit 2  16-bit samples, little-endian; strides stay in BYTES
+ *       bit 1  chroma not subsampled vertically           bit 3  no chroma planes (grey): U = V = mid-scale, u_base / v_base may be null
+ *   U(r, c) is the sample at u_base + (r >> sy) * c_row + (c >> sx) * c_pix with (sx, sy) = (1, 1) for 4:2:0 (word 0), (1, 0) for 4:2:2
+ *   (word 2; packed YUYV / UYVY is this with c_pix = 2 * y_pix), (0, 0) for 4:4:4 (word 3); P010 / P016 are word 4 with the NV12
+ *   addresses in bytes; the bits are orthogonal (16-bit 4:4:4 is word 7).  Values above 15, bit 3 together with bit 0 or 1, and an odd
+ *   base or stride of 16-bit samples are argument errors.  8-bit samples convert as above, grey with U = V = 128.  16-bit samples are
+ *   used as stored, s in [0, 65535] (P010: ten bits in the MSBs; whatever the low six bits hold counts), in int64:
+ *       yy = max(Y - 256 * YOFF, 0);  u = U - 32768;  v = V - 32768
+ *       R = clamp((CY * yy + CVR * v + (1 << 27)) >> 28, 0, 255)       G: CVG * v + CUG * u       B: CUB * u
+ *   so that a frame holding x << 8 converts to exactly the bytes the 8-bit rule gives for x.  Each sample is ONE 2-byte load; an
+ *   interleaved pair is never assumed to be 4-byte aligned.  Full-range and BT.2020 rows of coef, the closed form round(k * 2^20):
+ *   bt601-full (1048576, 1470104, -748826, -360853, 1858077, 0), bt709-full (1048576, 1651297, -490864, -196424, 1945738, 0),
+ *   bt2020-limited (1220945, 1760217, -682019, -196426, 2245811, 16), bt2020-full (1048576, 1546230, -599107, -172546, 1972791, 0).
+ *   A launch whose frames all have word 0 runs the kernels it always ran; with any other word in the table ALL its frames go through
+ *   the general instantiations and cp_last_kernel() is preprocess_yuv_surfaces_kernel<vec4|scalar> (reid_crop_kernel<surfaces> for
+ *   cp_reid_crop_yuv_frames_f32; the selection stays reid_select_kernel<yuv>).  The cp_draw_* entry points, device and host, refuse a
+ *   non-zero word with an argument error that names `pad`: they write 8-bit 4:2:0 only.
+ * cp_yuv16_to_bgr_host: HOST only -- cp_yuv_to_bgr_host for n triples of 16-bit container values. */
 typedef struct cp_yuv_frame_desc {  /* 136 bytes */
     const unsigned char* y_base;    /* DEVICE address of Y(0,0) */
     long long y_row, y_pix;         /* bytes */
@@ -437,7 +456,7 @@ typedef struct cp_yuv_frame_desc {  /* 136 bytes */
     long long mid_off;              /* as cp_pre_desc: offset of the resized image in scratch, < 0: no resize */
     int H, W, NH, NW;
     double mi[6];                   /* inverted warp matrix (cp_invert_warp) */
-    int slot, pad;
+    int slot, pad;                  /* pad: the format word, 0 = 8-bit 4:2:0 */
 } cp_yuv_frame_desc;
 int cp_sizeof_yuv_frame_desc(void);
 int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* table_host, int N, const int* coef, unsigned char* scratch,
@@ -445,6 +464,8 @@ int cp_preprocess_yuv_frames_u8_f32(const void* table, const void* table_host, i
                                     int flip, void* stream);
 int cp_yuv_to_bgr_host(const unsigned char* y, const unsigned char* u, const unsigned char* v, size_t n, const int* coef,
                        unsigned char* bgr);
+int cp_yuv16_to_bgr_host(const unsigned short* y, const unsigned short* u, const unsigned short* v, size_t n, const int* coef,
+                         unsigned char* bgr);
 
 /* ---- draw the detections onto device frames, in place (draw_results / run_batch(draw=True)) ------------------------------------------
  * The box, the 18 limbs and the 17 joints of every row of rows[N,M,56] (box 0:4, score 4, joints 5:39, joint scores 39:56, image
