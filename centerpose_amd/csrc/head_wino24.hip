@@ -55,10 +55,36 @@ struct HwGrid {
 __device__ __forceinline__ hw_v4 hw_lds4(const float* p) { return *reinterpret_cast<const hw_v4*>(p); }
 __device__ __forceinline__ int hw_div(int n, int d, unsigned magic) { return d == 1 ? n : (int)__umulhi((unsigned)n, magic); }
 
-// N2: outputs of the 1x1 on the register path (MM: outputs 32 .. 32 + N2 - 1); MM = 1: second MFMA phase for outputs 0..31
-template <int N2, int MM>
+// Staggered form: the wave's share of the output columns 2P, 2P + 1 (A4 restricted to its three frequencies) -> red[wave][col][tile][36]
+// at wq.  The same expressions as in the lock-step loops of the kernel.
+__device__ __forceinline__ void hw_write_share(const f32x16 (&acc)[3], const int vh, const int P, float* wq)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        hw_v4 q[3];
+#pragma unroll
+        for (int nu = 0; nu < 3; ++nu) q[nu] = (hw_v4){acc[nu][4 * j], acc[nu][4 * j + 1], acc[nu][4 * j + 2], acc[nu][4 * j + 3]};
+        hw_v4 c0, c1;
+        if (vh == 0) {                                   // m0, m1, m2
+            const hw_v4 s1 = q[1] + q[2], d1 = q[1] - q[2];
+            c0 = P == 0 ? q[0] + s1 : s1;
+            c1 = d1;
+        } else {                                         // m3, m4, m5
+            const hw_v4 s2 = q[0] + q[1], d2 = q[0] - q[1];
+            c0 = P == 0 ? s2 : 4.f * s2;
+            c1 = P == 0 ? 2.f * d2 : 8.f * d2 + q[2];
+        }
+        *reinterpret_cast<hw_v4*>(wq + 8 * j) = c0;
+        *reinterpret_cast<hw_v4*>(wq + 32 * HW_LDR + 8 * j) = c1;
+    }
+}
+
+// N2: outputs of the 1x1 on the register path (MM: outputs 32 .. 32 + N2 - 1); MM = 1: second MFMA phase for outputs 0..31;
+// STAG (MM = 0 only): waves 4-7 run half a channel tile behind waves 0-3 (see the loop); same sums in the same order, same bits
+template <int N2, int MM, bool STAG>
 __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvArgs a, const HwGrid gd, const HwHead hd)
 {
+    static_assert(!(STAG && MM), "the second-MFMA-phase form has no staggered variant");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int xi = wv & 3, vh = wv >> 2;
@@ -104,6 +130,9 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
 #pragma unroll
     for (int nu = 0; nu < 3; ++nu) bq[0][nu] = ig_ldg4(up + nu * 256);
     __syncthreads();
+    if constexpr (STAG) {
+        if (vh == 1) __syncthreads();   // barrier X: waves 4-7 form their V after waves 0-3, beside those waves' first MFMAs
+    }
 
     // ---- V for the wave's row xi and frequencies 3 vh .. 3 vh + 2, all 8 chunks, kept in registers
     const int rA = xi == 0 ? 0 : (xi == 2 ? 2 : 1);
@@ -156,7 +185,11 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
         for (int nu = 0; nu < 3; ++nu) asm volatile("" : "+v"(vl[kc][nu]), "+v"(vhh[kc][nu]));     // keep the chunk's transform here (cf. conv3x3_wino_vs64_kernel)
         __builtin_amdgcn_sched_barrier(0);                    // ... and the next chunk's patch reads behind it (all 80 hoisted = 320 VGPRs in flight)
     }
-    __syncthreads();                // every wave has read its rows of the patch: the region becomes the reduction buffers / mid
+    if constexpr (STAG) {
+        if (vh == 0) __syncthreads();   // barrier X, the other side.  The patch stays live: waves 4-7 read it until they enter their tile 0
+    } else {
+        __syncthreads();            // every wave has read its rows of the patch: the region becomes the reduction buffers / mid
+    }
 
     float acc2[2][2][N2 > 0 ? N2 : 1];                      // [pass][row aa][output] partial sums of the register-path 1x1
 #pragma unroll
@@ -209,6 +242,101 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
                 }
             }
         };
+        if constexpr (STAG) {
+            // ---- staggered form.  Waves wv and wv + 4 share a SIMD and, in lock-step, want its matrix pipe at the same time and leave it
+            // at the same time.  Here group A (waves 0-3) and group B (waves 4-7) run the SAME per-wave work half a tile apart, so a
+            // group's tile boundary (A4 arithmetic, 16 ds_write_b128, the loads of scale / shift / w2) falls beside the other group's
+            // MFMA chunks.  Two block-wide barriers per tile, as in lock-step, but half a tile apart in time:
+            //   Q(t - 1)  A: after chunk 4 of its tile t      B: before chunk 0 of its tile t     (Q(-1) releases B into its tile 0)
+            //   P(t)      A: after chunk 7 of its tile t      B: after chunk 3 of its tile t
+            //   Q(T - 1)  both groups, after their last shares (T = NTILES)
+            // Every wave crosses 2 T + 1 of them (plus barrier X of the prologue).  In program order of either group:
+            //   ... Q(t - 1) | reduction of tile t - 1 (A: chunks 5-7, B: chunks 0-3 of tile t) | P(t) | shares of tile t (A at once,
+            //   B four chunks later, after ITS chunk 7) | Q(t) | reduction of tile t | P(t + 1) | shares of tile t + 1 ...
+            // Lifetime of red[wave][..] (both buffers; each wave writes only its own regions, every thread reads all eight):
+            //   * write -> read: a wave's shares of tile t precede its arrival at Q(t); all reads of tile t follow Q(t);
+            //   * read -> next write: every thread's reads of tile t precede its arrival at P(t + 1); all writes of tile t + 1 follow it;
+            //   * the first shares overlay the halo patch: every wave's V (its last patch read) precedes its arrival at P(0).
+            // A reaches Q one chunk (12 MFMAs) after the point where B, half a tile behind, ends its tile: B's boundary work has that
+            // chunk before anyone waits for it, and when a group does wait at a barrier the other one is inside its MFMA loop.
+            // Per thread: tiles in ascending order into acc2, the eight shares in the lock-step order, the same expressions: same bits.
+            auto chunk = [&](const int kc, f32x16 (&acc)[3], auto&& ride) __attribute__((always_inline)) {
+                ++lin;
+                const float* un = up + (size_t)(lin < nlin ? lin : nlin - 1) * 1536;      // next chunk (next tile's first after the 8th)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int nu = 0; nu < 3; ++nu) {
+                    if (nu == 1) {                                   // next chunk's U after 4 of the chunk's 12 MFMAs
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(un + q * 256);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (nu == 2) {                                   // a piece of the previous tile's reduction rides here
+                        ride();
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    const float4 bbv = bq[kc & 1][nu];
+                    acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(bbv.x, vl[kc][nu].x, acc[nu], 0, 0, 0);
+                    acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(bbv.y, vl[kc][nu].y, acc[nu], 0, 0, 0);
+                    acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(bbv.z, vhh[kc][nu].x, acc[nu], 0, 0, 0);
+                    acc[nu] = __builtin_amdgcn_mfma_f32_32x32x2f32(bbv.w, vhh[kc][nu].y, acc[nu], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            auto tile_end = [&](const int nt, const f32x16 (&acc)[3], const bool barrier_first) __attribute__((always_inline)) {
+                const int ncol = nt * 32 + n4 * 4;                   // this tile's scale / shift / 1x1 weights, consumed in the next tile
+                sc = *reinterpret_cast<const hw_v4*>(a.scale + ncol);
+                sh = *reinterpret_cast<const hw_v4*>(a.shift + ncol);
+#pragma unroll
+                for (int j = 0; j < N2; ++j) w2r[j] = *reinterpret_cast<const hw_v4*>(hd.w2 + (size_t)j * hd.ld2 + ncol);
+                if (barrier_first) __syncthreads();                  // P(nt), group A
+#pragma unroll
+                for (int P = 0; P < 2; ++P) {
+                    int wbase = wpo + P * HW_RED;
+                    asm volatile("" : "+v"(wbase));                  // opaque base, as in red_read
+                    hw_write_share(acc, vh, P, smem + wbase);
+                }
+            };
+            const auto nothing = [] {};
+            if (vh == 0) {
+#pragma unroll 1
+                for (int nt = 0; nt < NTILES; ++nt) {
+                    const bool prev = nt > 0;
+                    f32x16 acc[3];
+#pragma unroll
+                    for (int nu = 0; nu < 3; ++nu)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[nu][r] = 0.f;
+#pragma unroll
+                    for (int kc = 0; kc < 5; ++kc) chunk(kc, acc, nothing);
+                    __syncthreads();                                 // Q(nt - 1)
+                    chunk(5, acc, [&] { if (prev) red_read(0); });
+                    chunk(6, acc, [&] { if (prev) { red_sum(0); red_read(1); } });
+                    chunk(7, acc, [&] { if (prev) red_sum(1); });
+                    tile_end(nt, acc, true);
+                }
+            } else {
+#pragma unroll 1
+                for (int nt = 0; nt < NTILES; ++nt) {
+                    const bool prev = nt > 0;
+                    f32x16 acc[3];
+#pragma unroll
+                    for (int nu = 0; nu < 3; ++nu)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[nu][r] = 0.f;
+                    __syncthreads();                                 // Q(nt - 1)
+                    chunk(0, acc, [&] { if (prev) red_read(0); });
+                    chunk(1, acc, [&] { if (prev) red_sum(0); });
+                    chunk(2, acc, [&] { if (prev) red_read(1); });
+                    chunk(3, acc, [&] { if (prev) red_sum(1); });
+                    __syncthreads();                                 // P(nt)
+#pragma unroll
+                    for (int kc = 4; kc < 8; ++kc) chunk(kc, acc, nothing);
+                    tile_end(nt, acc, false);
+                }
+            }
+            __syncthreads();                                         // Q(NTILES - 1): shares of the last tile complete
+        } else {
 #pragma unroll 1
         for (int nt = 0; nt < NTILES; ++nt) {
             const bool prev = nt > 0;
@@ -276,6 +404,7 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
                 }
             }
             __syncthreads();                                         // shares of tile nt complete
+        }
         }
         red_read(0); red_sum(0);                                     // the last tile's reduction has no MFMA loop to hide in
         red_read(1); red_sum(1);
@@ -435,13 +564,13 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
 
 static unsigned hw_magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
-template <int N2, int MM>
+template <int N2, int MM, bool STAG = false>
 static int launch_head_wino24(const ConvArgs& a, hipStream_t s, const HwHead& hd)
 {
     const int smem = (MM ? HW_SMEM_FLOATS_MM : HW_SMEM_FLOATS) * 4;
     static CpLdsGuard guard;
     {
-        const hipError_t e = guard.ensure((const void*)head_wino24_kernel<N2, MM>, smem);
+        const hipError_t e = guard.ensure((const void*)head_wino24_kernel<N2, MM, STAG>, smem);
         if (e != hipSuccess) { cp_set_error("head_wino24: cannot reserve %d B LDS: %s", smem, hipGetErrorString(e)); return 2; }
     }
     HwGrid gd;
@@ -450,8 +579,8 @@ static int launch_head_wino24(const ConvArgs& a, hipStream_t s, const HwHead& hd
     const long long grid = (long long)a.B * gd.tilesX * gd.tilesY;
     const long long dmax = gd.tilesX > gd.tilesY ? gd.tilesX : gd.tilesY;
     if (grid * dmax >= (1ll << 32)) { cp_set_error("head_wino24: grid %lld too large", grid); return 1; }
-    hipLaunchKernelGGL((head_wino24_kernel<N2, MM>), dim3((unsigned)grid), dim3(HW_THREADS), smem, s, a, gd, hd);
-    cp_note_kernel("head_wino24_kernel<%d, %d>", N2, MM);
+    hipLaunchKernelGGL((head_wino24_kernel<N2, MM, STAG>), dim3((unsigned)grid), dim3(HW_THREADS), smem, s, a, gd, hd);
+    cp_note_kernel("head_wino24_kernel<%d, %d>", N2, MM);          // the same name for both forms: STAG changes timing, not results
     return 0;
 }
 
@@ -467,8 +596,15 @@ int cp_launch_head3x3_1x1_w24(const ConvArgs& a, const float* w2, const float* b
     if (!ok) return -1;
     HwHead hd;
     hd.w2 = w2; hd.b2 = b2; hd.out2 = out2; hd.n2 = n2; hd.ld2 = ld2; hd.act2 = act2;
-    if (n2 == 1) return launch_head_wino24<1, 0>(a, s, hd);
-    if (n2 == 2) return launch_head_wino24<2, 0>(a, s, hd);
+    // CP_HEAD_STAGGER=0: the lock-step form of the n2 <= 2 kernels (A/B switch: tests compare the two bit for bit; read per call --
+    // launches are recorded once per plan, not per step).  The second-MFMA-phase kernels (n2 > 2) have the lock-step form only.
+    // Staggered is the default where it measured faster (profiles/head_stagger_ab.txt; DLA-34 512^2, B = 16, 1 024 blocks, one-stream
+    // rocprofv3 averages, lock-step -> staggered, two runs each): <2, 0> 274.7 / 274.8 -> 256.2 / 257.1 us, <1, 0> 266.4 / 267.2 ->
+    // 249.2 / 249.9 us; the step 7.12-7.17 -> 7.06-7.11 ms over three alternating runs each.
+    const char* sw = getenv("CP_HEAD_STAGGER");
+    const bool stag = !(sw && sw[0] == '0');
+    if (n2 == 1) return stag ? launch_head_wino24<1, 0, true>(a, s, hd) : launch_head_wino24<1, 0>(a, s, hd);
+    if (n2 == 2) return stag ? launch_head_wino24<2, 0, true>(a, s, hd) : launch_head_wino24<2, 0>(a, s, hd);
     if (n2 <= 32) return launch_head_wino24<0, 1>(a, s, hd);
     if (n2 == 33) return launch_head_wino24<1, 1>(a, s, hd);
     return launch_head_wino24<2, 1>(a, s, hd);
