@@ -14,8 +14,9 @@
 
 // per-thread description of the output pixels whose A rows this thread stages
 struct PixSlot {
-    int boff;   // b*H*W (input pixel index of the image origin), -1 if m >= M
+    int pix0;   // input pixel index of tap (0,0): b*H*W + iy0*W + ix0 (may lie outside the image; a valid tap's sum does not)
     int iy0, ix0;
+    bool live;  // m < M
 };
 
 // one block of the launch described by `a`: tile `tile` (already XCD-remapped) of `nblocks`
@@ -70,10 +71,11 @@ __device__ __forceinline__ void igemm_conv_block(const ConvArgs& a, int tile, in
             const int m = m0 + (tid >> 2) + s * 64;
             if (m < a.M) {
                 const int b = m / HoWo, p = m - b * HoWo, oy = p / a.Wo, ox = p - oy * a.Wo;
-                ps[s].boff = b * a.H * a.W;
                 ps[s].iy0 = oy * a.sy - pys;
                 ps[s].ix0 = ox * a.sx - pxs;
-            } else { ps[s].boff = -1; ps[s].iy0 = 0; ps[s].ix0 = 0; }
+                ps[s].pix0 = b * a.H * a.W + ps[s].iy0 * a.W + ps[s].ix0;
+                ps[s].live = true;
+            } else { ps[s].pix0 = 0; ps[s].iy0 = 0; ps[s].ix0 = 0; ps[s].live = false; }
         }
         float4 ar[T::A_SLOTS];
         bool aok[T::A_SLOTS];
@@ -98,19 +100,24 @@ __device__ __forceinline__ void igemm_conv_block(const ConvArgs& a, int tile, in
         auto load_a = [&]() __attribute__((always_inline)) {
             if (cl == 0 || fresh) {
                 fresh = false;
+                const int tapp = ky * a.W + kx;        // scalar: the tap's pixel offset from the slot's tap-(0,0) pixel
 #pragma unroll
                 for (int s = 0; s < T::A_SLOTS; ++s) {
                     const int iy = ps[s].iy0 + ky, ix = ps[s].ix0 + kx;
-                    const bool ok = ps[s].boff >= 0 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+                    const bool ok = ps[s].live && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
                     // branch-free: out-of-range taps read the (always valid) tensor base and are zeroed at store time
-                    aoff[s] = ok ? ((unsigned)(ps[s].boff + iy * a.W + ix) * (unsigned)ld + (unsigned)q * 4u) * 4u : 0u;
+                    aoff[s] = ok ? ((unsigned)(ps[s].pix0 + tapp) * (unsigned)ld + (unsigned)q * 4u) * 4u : 0u;
                     aok[s] = ok;
                 }
             }
             const char* xs = reinterpret_cast<const char*>(sp) + (size_t)cl * 4;      // uniform
 #pragma unroll
-            for (int s = 0; s < T::A_SLOTS; ++s)
+            for (int s = 0; s < T::A_SLOTS; ++s) {
+                // (keeps the offset a 32-bit value of THIS block: once the compiler widens it across the segment-start branch into a
+                // 64-bit merge, the gather loses its scalar-base form and pays a v_lshl_add_u64)
+                asm("" : "+v"(aoff[s]));
                 ar[s] = ig_ldg4(reinterpret_cast<const float*>(xs + aoff[s]));      // raw; a select here would wait on vmcnt
+            }
         };
         auto advance = [&]() __attribute__((always_inline)) {
             cl += IG_BK;
@@ -127,27 +134,56 @@ __device__ __forceinline__ void igemm_conv_block(const ConvArgs& a, int tile, in
                 *reinterpret_cast<float4*>(As + pl * IG_LDK + q * 4) = aok[s] ? ar[s] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         };
-
-        load_a(); advance();
-        ig_load_b<T>(a, ks0 * IG_BK, n0, tid, br, wsub);
-        store_a(As0);
-        ig_store_b<T>(Bs0, tid, br);
-        __syncthreads();
-        int cur = 0;
-        for (int ks = ks0; ks < nk; ++ks) {
-            const bool more = ks + 1 < nk;
-            ig_compute<T, MF>(As0 + cur * T::A_FLOATS, Bs0 + cur * T::B_FLOATS, wm0, wn0, lane, acc, [&]() __attribute__((always_inline)) {
-                if (more) { load_a(); advance(); ig_load_b<T>(a, (ks + 1) * IG_BK, n0, tid, br, wsub); }
+        // weight slice of a k-step: the thread's byte offset inside the packed matrix is fixed, the k offset rides in the SCALAR
+        // base (global_load v, v_off, s[base]: no 64-bit address VALU per k-step; the launcher checks 32-bit byte offsets)
+        unsigned boffw[T::B_SLOTS];
+#pragma unroll
+        for (int s = 0; s < T::B_SLOTS; ++s) {
+            const int idx = tid + s * IG_THREADS;
+            boffw[s] = ((unsigned)(n0 + (idx >> 2)) * (unsigned)a.K + (unsigned)(idx & 3) * 4u) * 4u;
+        }
+        // (a loop-carried scalar pointer: written as wsub + ks * 64 the compiler hoists (wsub + offset) into a 64-bit vector address)
+        const char* wb = reinterpret_cast<const char*>(wsub) + (size_t)ks0 * (IG_BK * 4);      // uniform
+        auto load_b = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int s = 0; s < T::B_SLOTS; ++s)
+                if (T::B_F4 % IG_THREADS == 0 || tid + s * IG_THREADS < T::B_F4) {
+                    asm("" : "+v"(boffw[s]));      // a 32-bit offset of this block, as for the gathers
+                    br[s] = ig_ldg4(reinterpret_cast<const float*>(wb + boffw[s]));
+                }
+            wb += IG_BK * 4;
+        };
+        // one k-step on compile-time LDS buffers: fragments from (Ar, Br), the next slice staged into (Aw, Bw)
+        auto kstep = [&](bool more, const float* Ar, const float* Br, float* Aw, float* Bw) __attribute__((always_inline)) {
+            ig_compute<T, MF>(Ar, Br, wm0, wn0, lane, acc, [&]() __attribute__((always_inline)) {
+                if (more) { load_a(); advance(); load_b(); }
             });
             // nothing that consumes the prefetched registers may be scheduled above the MFMAs (the blend /
             // zero-select would drag an s_waitcnt vmcnt in front of them and expose the whole load latency)
             __builtin_amdgcn_sched_barrier(0);
             if (more) {
-                store_a(As0 + (cur ^ 1) * T::A_FLOATS);
-                ig_store_b<T>(Bs0 + (cur ^ 1) * T::B_FLOATS, tid, br);
+                store_a(Aw);
+                ig_store_b<T>(Bw, tid, br);
             }
             __syncthreads();
-            cur ^= 1;
+        };
+
+        // unrolled by two so that both LDS buffers are compile-time constants (fragment reads and staging writes are lane base +
+        // immediate, no per-step buffer toggle).  An odd count runs its first step out of buffer 1, where the prologue then put it,
+        // so the pairs always start in buffer 0.
+        float* const As1 = As0 + T::A_FLOATS;
+        float* const Bs1 = Bs0 + T::B_FLOATS;
+        const bool odd = (nk - ks0) & 1;
+        load_a(); advance();
+        load_b();
+        store_a(odd ? As1 : As0);
+        ig_store_b<T>(odd ? Bs1 : Bs0, tid, br);
+        __syncthreads();
+        int ks = ks0;
+        if (odd) { kstep(ks + 1 < nk, As1, Bs1, As0, Bs0); ++ks; }
+        for (; ks < nk; ks += 2) {
+            kstep(true, As0, Bs0, As1, Bs1);
+            kstep(ks + 2 < nk, As1, Bs1, As0, Bs0);
         }
     } else {
         // ---------------- stem producer: NCHW input, tiny C (3): k = (c*kh + ky)*kw + kx ------
@@ -349,6 +385,8 @@ static int conv_args_from_desc(const cp_conv_desc* d, const float* const* src, c
                      (long long)d->B * d->srcC[0] * d->H * d->W, (1ll << 31) - 1);
     for (int i = 0; i < d->nsrc && !d->inNCHW; ++i)
         CP_CHECK_ARG((long long)d->B * d->H * d->W * d->srcLd[i] * 4 < (1ll << 32), "conv2d: source %d exceeds 32-bit byte offsets", i);
+    // packed weights [ldw][K]: the generic kernel's per-thread weight offset is a 32-bit byte offset
+    CP_CHECK_ARG((long long)d->ldw * d->K * 4 < (1ll << 32), "conv2d: packed weights of ldw*K=%lld floats exceed 32-bit byte offsets", (long long)d->ldw * d->K);
     CP_CHECK_ARG(!(res && d->outNCHW), "conv2d: residual with NCHW output is not supported");
     return 0;
 }

@@ -158,6 +158,9 @@ __global__ __launch_bounds__(IG_THREADS, 3) void dcn_igemm_kernel(const ConvArgs
         const char* xs = reinterpret_cast<const char*>(x) + (size_t)cl * 4;      // uniform
 #pragma unroll
         for (int s = 0; s < ASL; ++s) {
+            // (keeps the offsets 32-bit values of THIS block: once the compiler widens them across the tap-start branch into 64-bit
+            // merges, the gathers lose their scalar-base form and each pays a v_lshl_add_u64 and a v_mov)
+            asm("" : "+v"(o00[s]), "+v"(o01[s]), "+v"(o10[s]), "+v"(o11[s]));
             c00[s] = ig_ldg4(reinterpret_cast<const float*>(xs + o00[s]));
             c01[s] = ig_ldg4(reinterpret_cast<const float*>(xs + o01[s]));
             c10[s] = ig_ldg4(reinterpret_cast<const float*>(xs + o10[s]));
@@ -191,33 +194,49 @@ __global__ __launch_bounds__(IG_THREADS, 3) void dcn_igemm_kernel(const ConvArgs
         const int idx = tid + s * IG_THREADS;
         boff[s] = ((unsigned)(n0 + (idx >> 2)) * (unsigned)a.K + (unsigned)(idx & 3) * 4u) * 4u;
     }
-    auto load_b = [&](int ks) __attribute__((always_inline)) {
-        const char* wb = reinterpret_cast<const char*>(a.w) + (size_t)ks * (IG_BK * 4);      // uniform
+    // the base walks as a loop-carried scalar pointer: written as a.w + ks * 64 the compiler hoists (a.w + boff) into a 64-bit
+    // vector address and adds the k offset to it with one v_lshl_add_u64 per slot and k-step
+    const char* wb = reinterpret_cast<const char*>(a.w) + (size_t)ks0 * (IG_BK * 4);      // uniform
+    auto load_b = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < T::B_SLOTS; ++s)
-            if (T::B_F4 % IG_THREADS == 0 || tid + s * IG_THREADS < T::B_F4) br[s] = ig_ldg4(reinterpret_cast<const float*>(wb + boff[s]));
+            if (T::B_F4 % IG_THREADS == 0 || tid + s * IG_THREADS < T::B_F4) {
+                asm("" : "+v"(boff[s]));      // a 32-bit offset of this block, as for the gathers
+                br[s] = ig_ldg4(reinterpret_cast<const float*>(wb + boff[s]));
+            }
+        wb += IG_BK * 4;
     };
+    float* const As1 = As0 + T::A_FLOATS;
+    float* const Bs1 = Bs0 + T::B_FLOATS;
+    const bool odd = (nk - ks0) & 1;
     load_a(); advance();
-    load_b(ks0);
-    store_a(As0);
-    ig_store_b<T>(Bs0, tid, br);
+    load_b();
+    store_a(odd ? As1 : As0);
+    ig_store_b<T>(odd ? Bs1 : Bs0, tid, br);
     __syncthreads();
-    int cur = 0;
-    for (int ks = ks0; ks < nk; ++ks) {
-        const bool more = ks + 1 < nk;
+    // one k-step on compile-time LDS buffers: fragments from (Ar, Br), the next slice blended / staged into (Aw, Bw)
+    auto kstep = [&](bool more, const float* Ar, const float* Br, float* Aw, float* Bw) __attribute__((always_inline)) {
         // the next step's gathers are issued from inside the MFMA block (half-way through the k-step)
-        ig_compute<T, MF>(As0 + cur * T::A_FLOATS, Bs0 + cur * T::B_FLOATS, wm0, wn0, lane, acc, [&]() __attribute__((always_inline)) {
-            if (more) { load_a(); advance(); load_b(ks + 1); }
+        ig_compute<T, MF>(Ar, Br, wm0, wn0, lane, acc, [&]() __attribute__((always_inline)) {
+            if (more) { load_a(); advance(); load_b(); }
         });
         // nothing that consumes the prefetched registers may be scheduled above the MFMAs (the blend /
         // zero-select would drag an s_waitcnt vmcnt in front of them and expose the whole load latency)
         __builtin_amdgcn_sched_barrier(0);
         if (more) {
-            store_a(As0 + (cur ^ 1) * T::A_FLOATS);
-            ig_store_b<T>(Bs0 + (cur ^ 1) * T::B_FLOATS, tid, br);
+            store_a(Aw);
+            ig_store_b<T>(Bw, tid, br);
         }
         __syncthreads();
-        cur ^= 1;
+    };
+    // unrolled by two so that both LDS buffers are compile-time constants (fragment reads and staging writes are lane base +
+    // immediate, no per-step buffer toggle).  An odd count runs its first step out of buffer 1, where the prologue then put it,
+    // so the pairs always start in buffer 0.
+    int ks = ks0;
+    if (odd) { kstep(ks + 1 < nk, As1, Bs1, As0, Bs0); ++ks; }
+    for (; ks < nk; ks += 2) {
+        kstep(true, As0, Bs0, As1, Bs1);
+        kstep(ks + 2 < nk, As1, Bs1, As0, Bs0);
     }
     if (S > 1) {
         // raw partial sums of this split (the launcher passes scale = 1, shift = 0, no activation, NHWC with outLd = ldw)
