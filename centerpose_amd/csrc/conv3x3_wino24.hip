@@ -16,8 +16,11 @@
 //     [cg][py][px ^ s(py)][4] with s(py) = (py >> 1) & 3 on the low two bits of px and a row pitch of 20 float4: the 16 lanes of a
 //     ds_read_b128 group (4 tile columns x 4 tile rows) hit slot 4 * ((2 tyy + txx) & 3) + (j ^ tyy) mod 16 -- all distinct;
 //   * U = G2 g G4^T (cp_winograd24_pack_f32, fp64, rounded once) streams global -> registers in fragment order
-//     [xi][ntile][kc][nu 6][lane][4], one 8-channel chunk ahead, issued from inside the MFMA block;
-//   * per chunk and wave: 12 ds_read_b128 + 36 packed VALU + 6 global loads feed 24 v_mfma_f32_32x32x2f32;
+//     [xi][ntile][kc][nu 6][lane][4], one 8-channel chunk ahead, issued from inside the MFMA block: scalar chunk base + 32-bit lane offset;
+//   * the patch is read with buffer loads (32-bit lane offset, scalar channel offset); a halo slot outside the image lies past the
+//     descriptor's length and loads zero -- no zero-select (a tensor too wide for 32-bit offsets takes the *_far_kernel instantiations);
+//   * per chunk and wave: 12 ds_read_b128 + 36 packed VALU (no other VALU: 146 per 96 MFMAs in the listing, profiles/wino24_loop_ab.txt)
+//     + 6 global loads feed 24 v_mfma_f32_32x32x2f32; per stage 6 buffer loads and 6 ds_write_b128 per thread;
 //   * epilogue: the nu -> 4 output columns transform (A4) in registers, the xi-sum (A2) across the four waves through LDS in one
 //     pass, then scale / shift + residual + activation.
 // fp32 throughout.  F(4,3) has larger transform constants than F(2,3): the measured error against an fp64 convolution is in
@@ -44,6 +47,7 @@
 
 typedef float w24_v2 __attribute__((ext_vector_type(2)));
 typedef float w24_v4 __attribute__((ext_vector_type(4)));
+typedef unsigned w24_u4 __attribute__((ext_vector_type(4)));
 
 struct W24Grid {
     int tilesX, tilesY, ntb;
@@ -197,12 +201,13 @@ __device__ __forceinline__ void w24_output_all(const ConvArgs& a, float* red, co
     }
 }
 
-// Measured and NOT kept (same box, same process, tools/bench_conv.py): pinning the transform in front of the MFMA block with empty
-// asm statements, the literal -5 form of the column transform (two scalar v_fma_f32 per packed one), a run-time stage-buffer
-// offset (13 more address VALU per stage) -- all within the run-to-run noise of +-2 %: the kernel is not bound by its VALU count
-// (PMC: 63 % of a wave's cycles wait for issue behind the other resident waves / barriers, 20 % sit in s_waitcnt).
+// Measured and NOT kept (same box, same process, tools/bench_conv.py): the literal -5 form of the column transform (two scalar
+// v_fma_f32 per packed one), a run-time stage-buffer offset (13 more address VALU per stage) -- within the run-to-run noise of +-2 %
+// (PMC: 63 % of a wave's cycles wait for issue behind the other resident waves / barriers, 20 % sit in s_waitcnt).  MOVING VALU work
+// inside the loop never showed; REMOVING it did: 272 -> 146 non-MFMA VALU per pair of stages (scalar-base U loads, buffer-loaded patch
+// without select, all transform ops packed) is 61.5 -> 56.1 us per launch of the network (profiles/wino24_loop_ab.txt).
 // one block: tile t_ (already XCD-remapped) of the launch / group member described by (a, gd)
-template <bool FAST>
+template <bool FAST, bool FAR>
 __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, int t_, float* smem)
 {
     constexpr int CPS = W24_KS / 8;                    // chunks per stage
@@ -221,6 +226,13 @@ __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, 
     const bool interior = y0 >= 1 && y0 + 17 <= a.H && x0 >= 1 && x0 + 17 <= a.W;
 
     // ---- staging slots (fixed per thread): patch pixel pp, channel group q
+    // !FAR (every tensor whose 18-row patch spans less than 2 GiB: w24_far): the patch is read through a buffer descriptor based at the
+    // block's first patch pixel that lies inside the image, `nrec` bytes long (up to the last channel of the last such pixel).  A slot's
+    // byte offset is a 32-bit lane value, the stage's channel offset rides in the scalar offset -- no address VALU per stage -- and a
+    // halo slot outside the image has the offset 2^31 >= nrec: the load returns zero without touching memory, so the hand-over into
+    // LDS needs no zero-select on any tile.  FAR keeps 64-bit addresses and the select.
+    const int by0 = y0 > 0 ? y0 - 1 : 0, bx0 = x0 > 0 ? x0 - 1 : 0;                    // scalar
+    const int by1 = y0 + 16 < a.H ? y0 + 16 : a.H - 1, bx1 = x0 + 16 < a.W ? x0 + 16 : a.W - 1;
     int go[W24_SLOTS], lo[W24_SLOTS];
     bool ok[W24_SLOTS];
 #pragma unroll
@@ -231,17 +243,27 @@ __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, 
         const int gy = y0 - 1 + py, gx = x0 - 1 + px;
         const bool inl = idx < W24_F4;
         ok[s] = inl && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        go[s] = ok[s] ? ((b * a.H + gy) * a.W + gx) * ld + q * 4 : 0;
+        if constexpr (FAR) go[s] = ok[s] ? ((b * a.H + gy) * a.W + gx) * ld + q * 4 : 0;
+        else go[s] = ok[s] ? (((gy - by0) * a.W + (gx - bx0)) * ld + q * 4) * 4 : (int)0x80000000u;
         lo[s] = inl ? q * W24_CG + (py * W24_PWP + (px ^ ((py >> 1) & 3))) * 4 : -1;
     }
+    const int nrec = (((by1 - by0) * a.W + (bx1 - bx0)) * ld + C) * 4;
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(x) + ((size_t)(b * a.H + by0) * a.W + bx0) * ld, 0, FAR ? 0 : nrec, 0x00020000);
     float4 rg[W24_SLOTS];
     auto stage_load = [&](int c0) __attribute__((always_inline)) {
 #pragma unroll
-        for (int s = 0; s < W24_SLOTS; ++s) rg[s] = ig_ldg4(x + go[s] + c0);
+        for (int s = 0; s < W24_SLOTS; ++s) {
+            if constexpr (FAR) rg[s] = ig_ldg4(x + go[s] + c0);
+            else {
+                const w24_u4 v = __builtin_amdgcn_raw_buffer_load_b128(xrs, go[s], c0 * 4, 0);
+                rg[s] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+            }
+        }
     };
     auto stage_store = [&](float* buf) __attribute__((always_inline)) {
         // slots 0 .. SLOTS-2 are inside the patch for every thread ((s + 1) * 256 <= F4): only the last one needs the check
-        if (interior) {
+        if (!FAR || interior) {
 #pragma unroll
             for (int s = 0; s < W24_SLOTS; ++s)
                 if ((s + 1) * IG_THREADS <= W24_F4 || lo[s] >= 0) *reinterpret_cast<float4*>(buf + lo[s]) = rg[s];
@@ -272,17 +294,22 @@ __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, 
     // ---- U fragments: [xi][ntile][kc][nu 6][lane][4]
     int tile = nb;
     if (tile >= NTILES) tile = NTILES - 1;
-    const float* ub = a.w + ((size_t)(xi * NTILES + tile) * KC) * 1536 + lane * 4;
+    // the chunk base walks as a scalar pointer, the lane part is a 32-bit byte offset: global_load v, v_off, s[base] offset:nu * 1024.
+    // The base stops at the last chunk (the prefetch issued from the last chunk loads it again): no byte past the U buffer is read.
+    const char* ub = reinterpret_cast<const char*>(a.w + ((size_t)(xi * NTILES + tile) * KC) * 1536);      // uniform
+    // (nu = 4, 5 lie past the 4095-byte immediate: a second lane offset, or the compiler forms a 64-bit vector address for them per chunk)
+    unsigned uo = (unsigned)lane * 16u, uo4 = uo + 4096u;
     float4 bq[2][6];
-    auto load_u = [&](int kc, float4 (&dst)[6]) __attribute__((always_inline)) {
-        const int kk = kc < KC ? kc : KC - 1;
+    auto load_u = [&](bool advance, float4 (&dst)[6]) __attribute__((always_inline)) {
+        asm("" : "+v"(uo), "+v"(uo4));             // 32-bit offsets of this block (as dcn.hip's gathers)
 #pragma unroll
-        for (int nu = 0; nu < 6; ++nu) dst[nu] = ig_ldg4(ub + (size_t)kk * 1536 + nu * 256);
+        for (int nu = 0; nu < 6; ++nu) dst[nu] = ig_ldg4(reinterpret_cast<const float*>(ub + (nu < 4 ? uo : uo4) + (nu & 3) * 1024));
+        if (advance) ub += 1536 * 4;
     };
 
     const int nstage = C / W24_KS;
     stage_load(0);
-    load_u(0, bq[0]);
+    load_u(true, bq[0]);                               // KC >= 2
     stage_store(smem);
     if (tid < 4) *reinterpret_cast<float4*>(smem + W24_MAIN + tid * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
@@ -314,8 +341,8 @@ __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, 
             for (int j = 0; j < 6; ++j) {
                 const w24_v4 da = w24_lds4(pc + offA[j & 3] + (j >> 2) * 16);
                 const w24_v4 db = w24_lds4(pc + offB[j & 3] + (j >> 2) * 16);
-                tl[j] = __builtin_elementwise_fma(sg, db.xy, da.xy);
-                th[j] = __builtin_elementwise_fma(sg, db.zw, da.zw);
+                asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(tl[j]) : "v"(sg), "v"(db.xy), "v"(da.xy));
+                asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(th[j]) : "v"(sg), "v"(db.zw), "v"(da.zw));
             }
             // V = t B4: six column frequencies per channel pair in 12 packed ops, written so that every constant is an inline
             // operand of v_pk_fma_f32 (4, -4, 2, -2): 4 t0 - 5 t2 + t4 = 4 (t0 - t2) + (t4 - t2), 4 t1 - 5 t3 + t5 = (t5 - t3) - 4 (t3 - t1)
@@ -334,11 +361,15 @@ __device__ __forceinline__ void w24_block(const ConvArgs& a, const W24Grid& gd, 
                 vl[3] = __builtin_elementwise_fma(k2, fl, cl); vh[3] = __builtin_elementwise_fma(k2, fh, chh);
                 vl[4] = __builtin_elementwise_fma(kn2, fl, cl); vh[4] = __builtin_elementwise_fma(kn2, fh, chh);
             }
+            // all twelve operand pairs exist HERE: left alone the compiler sinks the ops of nu = 3 .. 5 behind the branches inside the
+            // MFMA block and splits each packed op it sinks into two scalar ones (38 packed -> 76 scalar VALU per pair of stages)
+#pragma unroll
+            for (int nu = 0; nu < 6; ++nu) asm volatile("" : "+v"(vl[nu]), "+v"(vh[nu]));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nu = 0; nu < 6; ++nu) {
                 if (nu == 1) {                                            // next chunk's U: after 4 of the 24 MFMAs
-                    load_u(st * CPS + ch + 1, bq[(ch + 1) & 1]);
+                    load_u(more, bq[(ch + 1) & 1]);           // chunk min(st * CPS + ch + 1, KC - 1)
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (nu == 3 && ch == 0 && more) {                         // next stage's patch: younger than every U load used in this stage
@@ -374,7 +405,14 @@ template <bool FAST>
 __global__ __launch_bounds__(IG_THREADS, 2) void conv3x3_wino24_kernel(const ConvArgs a, const W24Grid gd)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    w24_block<FAST>(a, gd, ig_xcd_remap(blockIdx.x, gridDim.x), smem);
+    w24_block<FAST, false>(a, gd, ig_xcd_remap(blockIdx.x, gridDim.x), smem);
+}
+// the same for a tensor whose patch rows lie too far apart for 32-bit byte offsets (w24_far)
+template <bool FAST>
+__global__ __launch_bounds__(IG_THREADS, 2) void conv3x3_wino24_far_kernel(const ConvArgs a, const W24Grid gd)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    w24_block<FAST, true>(a, gd, ig_xcd_remap(blockIdx.x, gridDim.x), smem);
 }
 
 // Up to four INDEPENDENT convolutions in one launch (HRNet: the same conv of every parallel branch, pose_higher_hrnet.py:217-235 --
@@ -387,16 +425,27 @@ struct W24Group {
     int first[5];
     int n;
 };
-template <bool FAST>
-__global__ __launch_bounds__(IG_THREADS, 2) void conv3x3_wino24_group_kernel(const W24Group g)
+template <bool FAST, bool FAR>
+__device__ __forceinline__ void w24_group_block(const W24Group& g, float* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     // NO XCD remap here: it hands each XCD a contiguous tile range, i.e. all of the longest member's blocks to XCD 0 (measured: 83 us per
     // group against 75 us for the four launches one by one); consecutive block ids go round-robin over the XCDs, which spreads every member
     const int t = blockIdx.x;
     int k = 0;
     while (k + 1 < g.n && t >= g.first[k + 1]) ++k;            // scalar
-    w24_block<FAST>(g.a[k], g.gd[k], t - g.first[k], smem);
+    w24_block<FAST, FAR>(g.a[k], g.gd[k], t - g.first[k], smem);
+}
+template <bool FAST>
+__global__ __launch_bounds__(IG_THREADS, 2) void conv3x3_wino24_group_kernel(const W24Group g)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    w24_group_block<FAST, false>(g, smem);
+}
+template <bool FAST>
+__global__ __launch_bounds__(IG_THREADS, 2) void conv3x3_wino24_group_far_kernel(const W24Group g)      // a member is w24_far
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    w24_group_block<FAST, true>(g, smem);
 }
 
 // the lean epilogue's preconditions (w24_output_all<true>)
@@ -406,6 +455,13 @@ static bool w24_fast_epilogue(const ConvArgs& a)
            (!a.res || ((a.resLd & 3) == 0 && (((size_t)a.res) & 15) == 0)) && (a.act == CP_ACT_NONE || a.act == CP_ACT_RELU) &&
            // w24_output_all<true> forms (4 * it + aa) * ostep, up to 13 output rows, in `int`
            (long long)a.W * a.outLd * 16 < (1ll << 31) && (long long)a.W * a.resLd * 16 < (1ll << 31);
+}
+
+// The kernels read the halo patch through 32-bit byte offsets from the block's first patch pixel; a tensor whose 18 patch rows span more
+// than 2 GiB (a very wide map of very few rows) takes the *_far_kernel instantiation with 64-bit addresses instead.
+static bool w24_far(const ConvArgs& a)
+{
+    return ((17ll * a.W + 17) * a.srcLd[0] + a.srcC[0]) * 4 > (1ll << 31);
 }
 
 static unsigned w24_magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
@@ -420,10 +476,12 @@ int cp_launch_conv3x3_wino24(const ConvArgs& a, hipStream_t s)
                     (long long)a.B * a.H * a.W * a.srcLd[0] < (1ll << 31);
     if (!ok) return -1;
     const int smem = W24_SMEM_FLOATS * 4;
-    const bool fast = w24_fast_epilogue(a);
-    static CpLdsGuard guard[2];
+    const bool fast = w24_fast_epilogue(a), far = w24_far(a);
+    static CpLdsGuard guard[4];
     {
-        const hipError_t e = guard[fast].ensure(fast ? (const void*)conv3x3_wino24_kernel<true> : (const void*)conv3x3_wino24_kernel<false>, smem);
+        const void* const fn = far ? (fast ? (const void*)conv3x3_wino24_far_kernel<true> : (const void*)conv3x3_wino24_far_kernel<false>)
+                                   : (fast ? (const void*)conv3x3_wino24_kernel<true> : (const void*)conv3x3_wino24_kernel<false>);
+        const hipError_t e = guard[2 * far + fast].ensure(fn, smem);
         if (e != hipSuccess) { cp_set_error("conv3x3_winograd24: cannot reserve %d B LDS: %s", smem, hipGetErrorString(e)); return 2; }
     }
     W24Grid gd;
@@ -433,6 +491,12 @@ int cp_launch_conv3x3_wino24(const ConvArgs& a, hipStream_t s)
     const long long grid = (long long)a.B * gd.tilesX * gd.tilesY * gd.ntb;
     const long long dmax = gd.ntb > gd.tilesX ? (gd.ntb > gd.tilesY ? gd.ntb : gd.tilesY) : (gd.tilesX > gd.tilesY ? gd.tilesX : gd.tilesY);
     if (grid * dmax >= (1ll << 32)) { cp_set_error("conv3x3_winograd24: grid %lld too large", grid); return 1; }
+    if (far) {
+        if (fast) hipLaunchKernelGGL(conv3x3_wino24_far_kernel<true>, dim3((unsigned)grid), dim3(IG_THREADS), smem, s, a, gd);
+        else hipLaunchKernelGGL(conv3x3_wino24_far_kernel<false>, dim3((unsigned)grid), dim3(IG_THREADS), smem, s, a, gd);
+        cp_note_kernel(fast ? "conv3x3_wino24_far_kernel<true>" : "conv3x3_wino24_far_kernel<false>");
+        return 0;
+    }
     if (fast) hipLaunchKernelGGL(conv3x3_wino24_kernel<true>, dim3((unsigned)grid), dim3(IG_THREADS), smem, s, a, gd);
     else hipLaunchKernelGGL(conv3x3_wino24_kernel<false>, dim3((unsigned)grid), dim3(IG_THREADS), smem, s, a, gd);
     cp_note_kernel(fast ? "conv3x3_wino24_kernel<true>" : "conv3x3_wino24_kernel<false>");      // as rocprofv3 prints the instantiation
@@ -445,7 +509,7 @@ int cp_launch_conv3x3_wino24_group(const ConvArgs* a, int n, hipStream_t s)
     if (n < 1 || n > 4) { cp_set_error("conv3x3_winograd24_group: 1..4 members (got %d)", n); return 1; }
     W24Group g;
     g.n = n;
-    bool fast = true;
+    bool fast = true, far = false;
     long long total = 0, dmax = 1;
     for (int i = 0; i < n; ++i) {
         const ConvArgs& c = a[i];
@@ -456,6 +520,7 @@ int cp_launch_conv3x3_wino24_group(const ConvArgs* a, int n, hipStream_t s)
         if (!ok) { cp_set_error("conv3x3_winograd24_group: member %d is not a 3x3 / stride 1 / pad 1 NHWC convolution", i); return 1; }
         g.a[i] = c;
         fast = fast && w24_fast_epilogue(c);
+        far = far || w24_far(c);
         W24Grid& gd = g.gd[i];
         gd.tilesX = cp_cdiv(c.W, 16); gd.tilesY = cp_cdiv(c.H, 16);
         gd.ntb = (c.Cout + 31) / 32;
@@ -471,10 +536,18 @@ int cp_launch_conv3x3_wino24_group(const ConvArgs* a, int n, hipStream_t s)
     for (int i = n; i < 4; ++i) { g.a[i] = g.a[0]; g.gd[i] = g.gd[0]; }
     if (total >= (1ll << 31)) { cp_set_error("conv3x3_winograd24_group: grid %lld too large", total); return 1; }
     const int smem = W24_SMEM_FLOATS * 4;
-    static CpLdsGuard guard[2];
+    static CpLdsGuard guard[4];
     {
-        const hipError_t e = guard[fast].ensure(fast ? (const void*)conv3x3_wino24_group_kernel<true> : (const void*)conv3x3_wino24_group_kernel<false>, smem);
+        const void* const fn = far ? (fast ? (const void*)conv3x3_wino24_group_far_kernel<true> : (const void*)conv3x3_wino24_group_far_kernel<false>)
+                                   : (fast ? (const void*)conv3x3_wino24_group_kernel<true> : (const void*)conv3x3_wino24_group_kernel<false>);
+        const hipError_t e = guard[2 * far + fast].ensure(fn, smem);
         if (e != hipSuccess) { cp_set_error("conv3x3_winograd24_group: cannot reserve %d B LDS: %s", smem, hipGetErrorString(e)); return 2; }
+    }
+    if (far) {
+        if (fast) hipLaunchKernelGGL(conv3x3_wino24_group_far_kernel<true>, dim3((unsigned)total), dim3(IG_THREADS), smem, s, g);
+        else hipLaunchKernelGGL(conv3x3_wino24_group_far_kernel<false>, dim3((unsigned)total), dim3(IG_THREADS), smem, s, g);
+        cp_note_kernel(fast ? "conv3x3_wino24_group_far_kernel<true>" : "conv3x3_wino24_group_far_kernel<false>");
+        return 0;
     }
     if (fast) hipLaunchKernelGGL(conv3x3_wino24_group_kernel<true>, dim3((unsigned)total), dim3(IG_THREADS), smem, s, g);
     else hipLaunchKernelGGL(conv3x3_wino24_group_kernel<false>, dim3((unsigned)total), dim3(IG_THREADS), smem, s, g);

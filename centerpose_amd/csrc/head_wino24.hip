@@ -124,11 +124,14 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
             }
     }
     // first U chunk in flight under the transform: [xi][ntile][kc][nu 6][lane][4]; the wave's three frequencies start at nu = 3 vh
-    const float* up = a.w + ((size_t)xi * NTILES * (HW_C / 8)) * 1536 + (size_t)(3 * vh) * 256 + lane * 4;
+    // (scalar base + 32-bit lane offset: global_load v, v_off, s[base] offset:nu * 1024 -- no 64-bit address VALU per chunk)
+    const char* const up = reinterpret_cast<const char*>(a.w + ((size_t)xi * NTILES * (HW_C / 8)) * 1536 + (size_t)(3 * vh) * 256);      // uniform
+    unsigned uo = (unsigned)lane * 16u;
+    const char* un = up;                                     // walks one chunk (1536 floats) at a time and stops at the wave's last chunk
     const int nlin = NTILES * (HW_C / 8);                    // chunks this wave walks through, 1536 floats apart
     float4 bq[2][3];
 #pragma unroll
-    for (int nu = 0; nu < 3; ++nu) bq[0][nu] = ig_ldg4(up + nu * 256);
+    for (int nu = 0; nu < 3; ++nu) bq[0][nu] = ig_ldg4(reinterpret_cast<const float*>(up + uo + nu * 1024));
     __syncthreads();
     if constexpr (STAG) {
         if (vh == 1) __syncthreads();   // barrier X: waves 4-7 form their V after waves 0-3, beside those waves' first MFMAs
@@ -262,13 +265,14 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
             // Per thread: tiles in ascending order into acc2, the eight shares in the lock-step order, the same expressions: same bits.
             auto chunk = [&](const int kc, f32x16 (&acc)[3], auto&& ride) __attribute__((always_inline)) {
                 ++lin;
-                const float* un = up + (size_t)(lin < nlin ? lin : nlin - 1) * 1536;      // next chunk (next tile's first after the 8th)
+                if (lin < nlin) un += 1536 * 4;      // next chunk (next tile's first after the 8th)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int nu = 0; nu < 3; ++nu) {
                     if (nu == 1) {                                   // next chunk's U after 4 of the chunk's 12 MFMAs
+                        asm("" : "+v"(uo));                          // a 32-bit offset of this block (as dcn.hip's gathers)
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(un + q * 256);
+                        for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(reinterpret_cast<const float*>(un + uo + q * 1024));
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (nu == 2) {                                   // a piece of the previous tile's reduction rides here
@@ -348,13 +352,14 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
 #pragma unroll
             for (int kc = 0; kc < HW_C / 8; ++kc) {
                 ++lin;
-                const float* un = up + (size_t)(lin < nlin ? lin : nlin - 1) * 1536;      // next chunk (next tile's first after the 8th)
+                if (lin < nlin) un += 1536 * 4;      // next chunk (next tile's first after the 8th)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int nu = 0; nu < 3; ++nu) {
                     if (nu == 1) {                                   // next chunk's U after 4 of the chunk's 12 MFMAs
+                        asm("" : "+v"(uo));                          // a 32-bit offset of this block (as dcn.hip's gathers)
 #pragma unroll
-                        for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(un + q * 256);
+                        for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(reinterpret_cast<const float*>(un + uo + q * 1024));
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (nu == 2 && prev) {                           // the previous tile's reduction rides between this tile's MFMAs
@@ -419,13 +424,14 @@ __global__ __launch_bounds__(HW_THREADS, 1) void head_wino24_kernel(const ConvAr
 #pragma unroll
         for (int kc = 0; kc < HW_C / 8; ++kc) {
             ++lin;
-            const float* un = up + (size_t)(lin < nlin ? lin : nlin - 1) * 1536;      // next chunk (next tile's first after the 8th)
+            if (lin < nlin) un += 1536 * 4;      // next chunk (next tile's first after the 8th)
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nu = 0; nu < 3; ++nu) {
                 if (nu == 1) {                                   // next chunk's U after 4 of the chunk's 12 MFMAs
+                    asm("" : "+v"(uo));
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(un + q * 256);
+                    for (int q = 0; q < 3; ++q) bq[(kc + 1) & 1][q] = ig_ldg4(reinterpret_cast<const float*>(un + uo + q * 1024));
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 const float4 bbv = bq[kc & 1][nu];
