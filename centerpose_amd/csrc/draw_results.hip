@@ -1,5 +1,6 @@
 // draw_results: the detections of N frames painted onto those frames, in place, on the device -- the box, the 18 limbs and the 17
-// joints of every row whose score is above vis_thresh (what the reference's show_results puts on the picture, without the text).
+// joints of every row whose score is above vis_thresh (what the reference's show_results puts on the picture; its score label and
+// its translucent limbs are the overlay painters of draw_overlay.hip).
 // The picture is defined by draw_arith.h: integer coverage tests, painter's order, opaque stores; a frame is never read.
 //
 //   cp_draw_rows_frames_u8      : frames addressed by cp_frame_desc (packed / planar BGR or RGB, 3 or 4 channels, any positive strides)

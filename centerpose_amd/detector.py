@@ -34,7 +34,7 @@ import torch
 from . import _lib
 from .decode import multi_pose_decode
 # frames.py and draw.py hold what used to be defined here: besides what this module uses, the names callers import from it stay
-from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv      # noqa: F401
+from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_OVERLAY, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv        # noqa: F401
 from .draw import TRACK_ITEM, TRACK_PALETTE, TrackStyle, draw_track_items                                            # noqa: F401
 from .frames import (FRAME_DESC, PRE_DESC, SURFACE_COLORS, SURFACE_MATRICES, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO,      # noqa: F401
                      _check_layout, byte_range, check_drawable, check_rows, frame_geometry, frame_writable, identity_table, is_yuv, yuv_coef,
@@ -372,7 +372,7 @@ class BaseDetector(object):
         raise NotImplementedError
 
     def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False, embed=None,
-                  track=None):
+                  track=None, draw_style=None):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -404,8 +404,15 @@ class BaseDetector(object):
         are painted with the tracker's result -- draw_results with the call's rows at TEST.VIS_THRESH and row_ids =
         track.row_ids(result, M), so that every matched pose takes its identity colour, then draw_tracks with `tracks` on top, both
         with their default styles.  The return value is exactly what it is without `draw`; the painting adds no synchronisation and
-        one table upload per painting call."""
+        one table upload per painting call.
+        draw_style (a DrawStyle; needs `draw`): what draw=True / draw="tracks" paint the rows with -- score labels, translucent limbs
+        (DrawStyle(labels=True, limb_opacity=128)); None is the default style, exactly as before.  The return value does not change."""
         given, io = images, self._io
+        if draw_style is not None:
+            if not isinstance(draw_style, DrawStyle):
+                raise _lib.CenterposeHipError("draw_style is a DrawStyle (got %s)" % type(draw_style).__name__)
+            if not draw:
+                raise ValueError("draw_style= is what draw=True / draw=\"tracks\" paint with: without `draw` nothing is painted")
         if draw:
             _check_layout(layout, color, matrix)
             check_drawable(color, matrix)
@@ -477,10 +484,11 @@ class BaseDetector(object):
             tracks = track.update(ordered, result, [(int(w), int(h)) for h, w in shapes])
         if draw == "tracks":
             ordered = ordered.contiguous()
-            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, None, row_ids=track.row_ids(result, int(ordered.shape[1])))
+            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, draw_style,
+                      row_ids=track.row_ids(result, int(ordered.shape[1])))
             draw_track_items(io, frames, tracks, color, matrix, None)
         elif draw:
-            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, None)
+            draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, draw_style)
         if return_device:
             return ordered if embed is None else (ordered, result) if track is None else (ordered, result, tracks)
         rows = rows.cpu().numpy()                                                               # the one download
@@ -492,17 +500,20 @@ class BaseDetector(object):
     def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None, row_ids=None,
                      id_palette=None):
         """Paint the detections `rows` onto `frames`, in place, on the device, in the current stream -> `frames`.  What is drawn is
-        what the reference's show_results draws, without the text: per row with score > vis_thresh (default cfg.TEST.VIS_THRESH) the
-        box, the limbs whose two joints both score > 0 and the joints that score > 0, opaque, rows in ascending order, box then limbs
-        then joints, the last painted wins.  The rule is this project's own, integer-only and bit-exact between the device, the host
-        painter cp_draw_rows_frames_host and a NumPy restatement (csrc/draw_arith.h).
+        what the reference's show_results draws: per row with score > vis_thresh (default cfg.TEST.VIS_THRESH) the box, the limbs
+        whose two joints both score > 0 and the joints that score > 0, opaque, rows in ascending order, box then limbs then joints,
+        the last painted wins; the score label on top of the box and translucent limbs are options of the style
+        (DrawStyle(labels=True, limb_opacity=128): csrc/draw_overlay_arith.h).  The rule is this project's
+        own, integer-only and bit-exact between the device, the host painter cp_draw_rows_frames_host and a NumPy restatement
+        (csrc/draw_arith.h).
         frames: as for pre_process_batch -- a list of CUDA uint8 tensors or one 4-D tensor (`layout`, `color`, C = 3 or 4), or with
         color "nv12" / "nv21" / "i420" a list of plane tuples / surface tensors; for those the palette is converted to (Y, U, V) with
         `matrix` (palette_to_yuv), luma is written per pixel and a chroma sample takes the latest-painted colour among its 2x2 pixels.
         The colours of frames.SURFACE_COLORS and the matrices of frames.SURFACE_MATRICES raise before anything is launched.
         Three bytes per covered pixel: a fourth channel, row padding and everything outside a view keep their bytes.
         rows: CUDA float32 [N, M, 56] in image coordinates, as run_batch(..., return_device=True) returns them ([M, 56]: one frame).
-        style: a DrawStyle.  The descriptor table is the only upload; nothing is downloaded and nothing synchronises.
+        style: a DrawStyle.  The descriptor table is the only upload; nothing is downloaded and nothing synchronises -- the label's
+        score is turned into glyphs on the device.
         A frame is WRITTEN here, so beyond the stream-order and lifetime rules of pre_process_batch, which hold unchanged: every tensor
         must be a view in which no two indices address one byte (frame_writable: expanded and overlapping views raise), a plane
         tuple's luma bytes must lie apart from its chroma bytes, the same tensor may not be given twice -- and that the frames of one

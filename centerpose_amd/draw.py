@@ -12,6 +12,9 @@ from .frames import YUV_COLORS, identity_table
 
 # cp_draw_style (include/centerpose_hip.h)
 DRAW_STYLE = np.dtype([("box_thickness", "<i4"), ("limb_radius", "<i4"), ("joint_radius", "<i4"), ("palette", "u1", (36, 4))])
+# cp_draw_overlay: what a DrawStyle holds beyond cp_draw_style -- the opacities of box, limbs and joints and the score label
+DRAW_OVERLAY = np.dtype([("opacity", "<i4", (3,)), ("label_scale", "<i4"), ("nprefix", "<i4"), ("prefix", "u1", (12,)), ("text_color", "u1", (4,))])
+MAX_LABEL_PREFIX = 9
 
 # the limbs of a pose in paint order, as joint pairs (COCO keypoint order: 0 nose, odd = left, even = right)
 DRAW_LIMBS = ((0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6), (5, 6), (5, 7), (7, 9), (6, 8), (8, 10), (5, 11), (6, 12), (11, 12), (11, 13),
@@ -29,9 +32,15 @@ class DrawStyle:
     """How draw_results paints: box_thickness 0..64 (0: no box), limb_radius -1 (no limbs) or 1..64, joint_radius -1 (no joints) or
     0..64, and the colours as (B, G, R): one for the box, one per limb (DRAW_LIMBS order), one per joint.  Defaults: thickness 2, limb
     radius 1, joint radius 2; a limb or joint on the left side DRAW_LEFT, on the right side DRAW_RIGHT, the box, the nose and the limbs
-    that join the two sides DRAW_MID."""
+    that join the two sides DRAW_MID.
+    labels=True writes label_prefix + '%.1f' % score on a filled bar on top of every box, in the box's colour, as the reference's
+    add_coco_bbox does: label_scale 1..8 pixels per cell of the 5 x 7 font, at most 9 prefix characters of CHARSET (lower case is
+    folded), the text in label_text_color.  box_opacity / limb_opacity / joint_opacity, 1..256: how much of its colour a primitive of
+    that class puts on a pixel, p' = (p (256 - a) + c a + 128) >> 8 per covering primitive; 256 stores the colour as before, 51 and
+    128 are the 0.2 and 0.5 of the reference's add_coco_hp.  A style that leaves these defaults paints through the plain entry points."""
 
-    def __init__(self, box_thickness=2, limb_radius=1, joint_radius=2, box_color=None, limb_colors=None, joint_colors=None):
+    def __init__(self, box_thickness=2, limb_radius=1, joint_radius=2, box_color=None, limb_colors=None, joint_colors=None, labels=False,
+                 label_prefix="person", label_scale=1, label_text_color=(0, 0, 0), box_opacity=256, limb_opacity=256, joint_opacity=256):
         self.box_thickness, self.limb_radius, self.joint_radius = int(box_thickness), int(limb_radius), int(joint_radius)
         self.box_color = tuple(box_color) if box_color is not None else DRAW_MID
         self.limb_colors = [tuple(c) for c in limb_colors] if limb_colors is not None else [_side_color(ab) for ab in DRAW_LIMBS]
@@ -44,9 +53,38 @@ class DrawStyle:
             raise _lib.CenterposeHipError("joint_radius %d outside -1..64" % self.joint_radius)
         if len(self.limb_colors) != 18 or len(self.joint_colors) != 17:
             raise _lib.CenterposeHipError("a style has 18 limb colours and 17 joint colours")
-        for c in self.palette():
+        self.labels, self.label_prefix, self.label_scale = bool(labels), str(label_prefix), int(label_scale)
+        self.label_text_color = tuple(int(v) for v in label_text_color)
+        self.box_opacity, self.limb_opacity, self.joint_opacity = int(box_opacity), int(limb_opacity), int(joint_opacity)
+        for c in self.palette() + [self.label_text_color]:
             if len(c) != 3 or any(not (0 <= int(v) <= 255) for v in c):
                 raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
+        if not 1 <= self.label_scale <= 8:
+            raise _lib.CenterposeHipError("label_scale %d outside 1..8 (labels=False draws none)" % self.label_scale)
+        for name in ("box_opacity", "limb_opacity", "joint_opacity"):
+            if not 1 <= getattr(self, name) <= 256:
+                raise _lib.CenterposeHipError("%s %d outside 1..256 (256: opaque)" % (name, getattr(self, name)))
+        if len(self.label_prefix) > MAX_LABEL_PREFIX:
+            raise _lib.CenterposeHipError("the label prefix %r has %d characters, at most %d are drawn"
+                                          % (self.label_prefix, len(self.label_prefix), MAX_LABEL_PREFIX))
+        try:
+            self.prefix_glyphs = label_glyphs(self.label_prefix)       # a prefix the font cannot write raises here, not at the first frame
+        except ValueError as e:
+            raise _lib.CenterposeHipError(str(e))
+
+    def needs_overlay(self):
+        """Whether the style leaves the defaults of cp_draw_style alone: labels, or a primitive class that is not opaque."""
+        return self.labels or (self.box_opacity, self.limb_opacity, self.joint_opacity) != (256, 256, 256)
+
+    def overlay_struct(self, matrix=None):
+        """One DRAW_OVERLAY record; `matrix`: the text colour as (Y, U, V) for YUV frames."""
+        rec = np.zeros(1, DRAW_OVERLAY)
+        rec["opacity"][0] = (self.box_opacity, self.limb_opacity, self.joint_opacity)
+        rec["label_scale"] = self.label_scale if self.labels else 0
+        rec["nprefix"] = len(self.prefix_glyphs)
+        rec["prefix"][0, :len(self.prefix_glyphs)] = self.prefix_glyphs
+        rec["text_color"][0, :3] = self.label_text_color if matrix is None else palette_to_yuv([self.label_text_color], matrix)[0]
+        return rec
 
     def palette(self):
         """The 36 (B, G, R) colours in paint order: the box, the limbs, the joints."""
@@ -98,7 +136,8 @@ def _id_palette_struct(colors, matrix):
 def draw_rows(io, frames, rows, color, matrix, vis_thresh, style, row_ids=None, id_palette=None):
     """cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8 for checked frames (`io.frame` / `io.yuv_frame` per image) and device rows
     [N,M,56]: one table upload through `io` (a FrameIO), two launches in the current stream.  row_ids (CUDA int32 [N,M]): the
-    cp_draw_rows_ids_* forms -- a row whose id is >= 0 is painted in id_palette[id % P] (default: TRACK_PALETTE)."""
+    cp_draw_rows_ids_* forms -- a row whose id is >= 0 is painted in id_palette[id % P] (default: TRACK_PALETTE).  A style with
+    labels or an opacity below 256 (DrawStyle.needs_overlay) goes through cp_draw_overlay_frames_u8 / cp_draw_overlay_yuv_frames_u8."""
     yuv = color in YUV_COLORS
     style = DrawStyle() if style is None else style
     if not isinstance(style, DrawStyle):
@@ -118,14 +157,20 @@ def draw_rows(io, frames, rows, color, matrix, vis_thresh, style, row_ids=None, 
     table = identity_table(frames, yuv)
     rec = style.struct(matrix if yuv else None)
     L = _lib.lib()
-    L.cp_draw_scratch_bytes.restype = ctypes.c_size_t
-    nbytes = int(L.cp_draw_scratch_bytes(N, M))
+    overlay = style.overlay_struct(matrix if yuv else None) if style.needs_overlay() else None
+    sizer = L.cp_draw_scratch_bytes if overlay is None else L.cp_draw_overlay_scratch_bytes
+    sizer.restype = ctypes.c_size_t
+    nbytes = int(sizer(N, M))
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=rows.device)
     table_dev, = io.upload_table([table])
     vp = ctypes.c_void_p
     head = (vp(table_dev.data_ptr()), table.ctypes.data_as(vp), N, vp(rows.data_ptr()), M, ctypes.c_float(float(vis_thresh)),
             rec.ctypes.data_as(vp), vp(scratch.data_ptr()), ctypes.c_size_t(nbytes))
-    if row_ids is None:
+    if overlay is not None:
+        name = "cp_draw_overlay_yuv_frames_u8" if yuv else "cp_draw_overlay_frames_u8"
+        ids = (vp(row_ids.data_ptr()), idp.ctypes.data_as(vp)) if row_ids is not None else (None, None)
+        rc = getattr(L, name)(*head, *ids, overlay.ctypes.data_as(vp), _lib.stream())
+    elif row_ids is None:
         name = "cp_draw_rows_yuv_frames_u8" if yuv else "cp_draw_rows_frames_u8"
         rc = getattr(L, name)(*head, _lib.stream())
     else:

@@ -534,6 +534,51 @@ int cp_draw_rows_ids_frames_host(const void* table_host, int N, const float* row
 int cp_draw_rows_ids_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
                                      const int* row_ids, const void* id_palette);
 
+/* ---- score labels and translucent poses: draw_results with an overlay (DrawStyle(labels=..., limb_opacity=...)) -----------------------
+ * What the reference's show_results adds to the boxes and skeletons above: '{prefix}{score:.1f}' on a filled bar on top of every box
+ * (Debugger.add_coco_bbox) and limbs blended into the picture (Debugger.add_coco_hp).  The rule is csrc/draw_overlay_arith.h:
+ *   primitives of a row in paint order: the 36 of cp_draw_style, then 36 the label bar and 37 the label text; paint index row * 38 + l.
+ *   blend: primitive l has an opacity a in 1..256 -- opacity[0] the box, [1] the limbs, [2] the joints, bar and text always 256 -- and a
+ *     covered channel byte p becomes (p * (256 - a) + c * a + 128) >> 8, once per covering primitive, in paint order (a = 256: c).  YUV
+ *     frames: luma per covered pixel; chroma sample (i, j) once per primitive that covers at least one in-frame pixel of its 2x2 block,
+ *     with that primitive's (U, V).  A frame is READ where a translucent primitive covers it and nothing opaque lies beneath.
+ *   label: a live row has one iff label_scale s is in 1..8 and its four box coordinates are alive (box_thickness plays no part).  With
+ *     (x0, y0) the box's sorted corner, n characters, tw = 6 s n - s, th = 7 s: the bar is the closed rectangle [x0, x0 + tw + 3] x
+ *     [y0 - th - 5, y0 - 1] in the colour the row's box takes (palette[0] or the identity colour); the text follows the glyph rule of
+ *     cp_draw_track_item with dx = x - (x0 + 2), dy = y - (y0 - th - 3), in text_color.  What leaves the frame is clipped.
+ *   text: prefix[0 .. nprefix - 1] (glyph indices, nprefix 0..9), then the score to one decimal by an integer rule on the float's bits:
+ *     with |score| = m 2^e exactly, t = min(round_half_even(10 m 2^e), 9999); ['-' if the sign bit is set] str(t / 10) '.' str(t % 10).
+ *     +-inf gives 999.9; this is '%.1f' for |score| < 999.95.  cp_draw_score_label runs it on the HOST: glyphs[0..5] -> nchars, -1 for NaN.
+ * cp_draw_overlay_frames_u8 / cp_draw_overlay_yuv_frames_u8: the arguments of cp_draw_rows_ids_*_u8 and `overlay`, a HOST cp_draw_overlay;
+ *   row_ids and id_palette may both be null.  Two launches on `stream` (draw_overlay_build_kernel: draw_build_kernel, which also turns
+ *   the score into the row's label record; draw_overlay_kernel: the tiles and pixel ownership of draw_raster_kernel, the topmost
+ *   opaque cover from the back, then the translucent primitives above it forward).  scratch: cp_draw_overlay_scratch_bytes(N, M).
+ *   Checked before anything is launched: all that cp_draw_rows_ids_* checks, a non-null overlay, opacities in 1..256, label_scale in
+ *   0..8, nprefix in 0..9, every prefix glyph inside the font, row_ids and id_palette both null or both non-null.  With opacities 256
+ *   and label_scale 0 the result equals cp_draw_rows_* / cp_draw_rows_ids_* byte for byte.  cp_last_kernel(): draw_overlay_kernel<bgr|yuv>.
+ * cp_draw_overlay_frames_host / cp_draw_overlay_yuv_frames_host: HOST only -- the sequential painters, same statements, same checks.
+ *   What the device result is pinned to, byte for byte. */
+typedef struct cp_draw_overlay {        /* 36 bytes */
+    int opacity[3];
+    int label_scale;
+    int nprefix;
+    unsigned char prefix[12];
+    unsigned char text_color[4];
+} cp_draw_overlay;
+int cp_sizeof_draw_overlay(void);
+size_t cp_draw_overlay_scratch_bytes(int N, int M);
+int cp_draw_score_label(float score, unsigned char* glyphs);
+int cp_draw_overlay_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                              const void* style, void* scratch, size_t scratch_bytes, const int* row_ids, const void* id_palette,
+                              const void* overlay, void* stream);
+int cp_draw_overlay_yuv_frames_u8(const void* table, const void* table_host, int N, const float* rows, int M, float vis_thresh,
+                                  const void* style, void* scratch, size_t scratch_bytes, const int* row_ids, const void* id_palette,
+                                  const void* overlay, void* stream);
+int cp_draw_overlay_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                const int* row_ids, const void* id_palette, const void* overlay);
+int cp_draw_overlay_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
+                                    const int* row_ids, const void* id_palette, const void* overlay);
+
 /* ---- draw tracks onto device frames, in place: box, label bar, label (draw_tracks / run_batch(draw="tracks")) --------------------------
  * What the reference's draw_bboxes puts on the picture per track, by this library's own integer rule (csrc/draw_text_arith.h) and its
  * own 5 x 7 font.  Frame n paints items[n][0 .. counts[n] - 1] of items[N][Kmax].  With box thickness T (0..64), font scale s (0..8,
