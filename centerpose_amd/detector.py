@@ -36,6 +36,7 @@ from .decode import multi_pose_decode
 # frames.py and draw.py hold what used to be defined here: besides what this module uses, the names callers import from it stay
 from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_OVERLAY, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv        # noqa: F401
 from .draw import TRACK_ITEM, TRACK_PALETTE, TrackStyle, draw_track_items                                            # noqa: F401
+from .draw import DRAW_HEAT_STYLE, HeatmapStyle, check_heat_maps, draw_heat                                          # noqa: F401
 from .frames import (FRAME_DESC, PRE_DESC, SURFACE_COLORS, SURFACE_MATRICES, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO,      # noqa: F401
                      _check_layout, byte_range, check_drawable, check_rows, frame_geometry, frame_writable, identity_table, is_yuv, yuv_coef,
                      yuv_frame_geometry, yuv_surface_geometry)
@@ -554,6 +555,35 @@ class BaseDetector(object):
                                           "there is no CPU fallback")
         io.check_writable(given, images, color)
         draw_track_items(io, descs or [], list(tracks), color, matrix, style)
+        return given
+
+    def draw_heatmaps(self, frames, maps, metas, scale=1, layout="hwc", color="bgr", matrix="bt601", style=None):
+        """Blend the heat maps `maps` over `frames`, in place, on the device, in the current stream -> `frames`.  The reference's debug
+        views pred_hm / pred_hmhp (MultiPoseDetector.debug): per image the maps become one colour map -- per component the maximum over
+        the channels of value x channel colour -- which is sampled bilinearly at the map position of every frame pixel and blended
+        over it, p' = (p (256 - a) + f a + 128) >> 8.  The rule is this project's own, bit-exact between the device, the host painter
+        cp_draw_heat_frames_host and a NumPy restatement (csrc/draw_heat_arith.h): map cell (i, j) sits at map
+        coordinate (i, j), where post_process puts a peak, so a blob lies under the joint draw_results paints for it.
+        frames: as for draw_results, with the same rules for writable frames; host arrays raise.  Every pixel is read and written; a
+        fourth channel, row padding and everything outside a view keep their bytes.  On color "nv12" / "nv21" / "i420" the colour goes
+        to (Y, U, V) with `matrix`, luma per pixel, a chroma sample with the mean colour of its 2x2 pixels.
+        maps: CUDA float32 [N, C, h, w] ([C, h, w]: one frame) on the model's device, 1 <= C <= 32, ANY non-negative strides -- never
+        copied, so outputs[0], outputs[4][0::2] (the images of a FLIP_TEST batch, not their twins), a channel slice or a permuted view go
+        in as they are.  metas: what pre_process_batch / pre_process returned for these frames at `scale`; their out_height / out_width
+        are the maps' h / w.  style: a HeatmapStyle.
+        The descriptor table is the only upload; nothing is downloaded and nothing synchronises.  Two launches."""
+        given, io = frames, self._io
+        _check_layout(layout, color, matrix)
+        check_drawable(color, matrix)
+        images, descs = io.batch_input(frames, layout, color, matrix)
+        if descs is None and images:
+            raise _lib.CenterposeHipError("draw_heatmaps paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
+                                          "there is no CPU fallback")
+        if isinstance(metas, dict):
+            metas = [metas]
+        maps = check_heat_maps(maps, len(images), io.device)
+        io.check_writable(given, images, color)
+        draw_heat(io, descs or [], maps, metas, lambda height, width: self.input_geometry(height, width, scale)[0:2], color, matrix, style)
         return given
 
     def _source(self, x, layout="hwc", color="bgr", matrix="bt601"):

@@ -1,6 +1,7 @@
 """The host side of drawing detections onto device frames: the style record, the palette (and its YUV form) and the launch of the
 painters of csrc/draw_results.hip over an identity descriptor table; and of drawing tracks: the track style, the identity palette, the
-item table of boxes and labels and the launch of csrc/draw_tracks.hip.  `BaseDetector.draw_results` / `draw_tracks` are the entry
+item table of boxes and labels and the launch of csrc/draw_tracks.hip; and of blending heat maps over frames: the heat-map style, the
+frame -> map matrices and the launch of csrc/draw_heat.hip.  `BaseDetector.draw_results` / `draw_tracks` / `draw_heatmaps` are the entry
 points."""
 import ctypes
 
@@ -283,4 +284,122 @@ def draw_track_items(io, frames, tracks, color, matrix, style):
     rc = getattr(_lib.lib(), name)(vp(table_dev.data_ptr()), table.ctypes.data_as(vp), N, vp(items_dev.data_ptr()), items.ctypes.data_as(vp),
                                    vp(counts_dev.data_ptr()), counts.ctypes.data_as(vp), Kmax, style.box_thickness, style.font_scale,
                                    _lib.stream())
+    _lib.check(rc, name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- heat maps over frames
+# cp_draw_heat_style (include/centerpose_hip.h)
+DRAW_HEAT_STYLE = np.dtype([("channels", "<i4"), ("opacity", "<i4"), ("invert", "<i4"), ("palette", "u1", (32, 4))])
+MAX_HEAT_CHANNELS = 32
+HEAT_MATRIX_IDS = {"bt601": 0, "bt709": 1}
+
+
+class HeatmapStyle:
+    """How draw_heatmaps paints: `colors`, at least one (B, G, R) per map channel (default: white for one channel, else the first C
+    entries of TRACK_PALETTE, cycling past its length); `opacity` 1..256, how much of the colour map a pixel takes, p' = (p (256 - a) +
+    f a + 128) >> 8 (179: the reference's 0.7, 256: the colour map alone); `invert`: the reference's white theme -- colours and colour
+    map are both taken from 255, so a silent map blends towards white and a peak towards its channel's colour."""
+
+    def __init__(self, colors=None, opacity=179, invert=False):
+        self.colors = None if colors is None else [tuple(int(v) for v in c) for c in colors]
+        self.opacity, self.invert = int(opacity), bool(invert)
+        if not 1 <= self.opacity <= 256:
+            raise _lib.CenterposeHipError("opacity %d outside 1..256 (256: the colour map alone)" % self.opacity)
+        if self.colors is not None and len(self.colors) > MAX_HEAT_CHANNELS:
+            raise _lib.CenterposeHipError("a heat-map style has at most %d colours (got %d)" % (MAX_HEAT_CHANNELS, len(self.colors)))
+        for c in self.colors or []:
+            if len(c) != 3 or any(not (0 <= v <= 255) for v in c):
+                raise _lib.CenterposeHipError("a colour is three values in 0..255, got %r" % (c,))
+
+    def palette(self, channels):
+        """The (B, G, R) colours of `channels` map channels."""
+        if not 1 <= channels <= MAX_HEAT_CHANNELS:
+            raise _lib.CenterposeHipError("%d map channels outside 1..%d" % (channels, MAX_HEAT_CHANNELS))
+        if self.colors is None:
+            return [(255, 255, 255)] if channels == 1 else [TRACK_PALETTE[c % len(TRACK_PALETTE)] for c in range(channels)]
+        if len(self.colors) < channels:
+            raise _lib.CenterposeHipError("the style has %d colours for %d map channels" % (len(self.colors), channels))
+        return self.colors[:channels]
+
+    def struct(self, channels):
+        """One DRAW_HEAT_STYLE record for maps of `channels` channels; the colours stay (B, G, R) for every kind of frame."""
+        rec = np.zeros(1, DRAW_HEAT_STYLE)
+        rec["channels"], rec["opacity"], rec["invert"] = channels, self.opacity, int(self.invert)
+        rec["palette"][0, :channels, :3] = np.asarray(self.palette(channels), np.uint8)
+        return rec
+
+
+def heat_transform(meta, height, width, new_h, new_w):
+    """float64 [6]: the frame -> map matrix of one height x width frame that the pre-process resized to new_h x new_w
+    (input_geometry) and whose meta is `meta`: get_affine_transform(c, s, 0, (out_width, out_height)), what maps the resized image onto
+    the output map, with its columns scaled by the resize (new_w / width, new_h / height).  Not finite: CenterposeHipError."""
+    from .post_process import get_affine_transform
+    T = np.array(get_affine_transform(meta["c"], meta["s"], 0, (meta["out_width"], meta["out_height"])), np.float64)
+    T[:, 0] *= float(new_w) / float(width)
+    T[:, 1] *= float(new_h) / float(height)
+    if not np.isfinite(T).all():
+        raise _lib.CenterposeHipError("the frame -> map matrix of a %d x %d frame is not finite: %s" % (height, width, T.reshape(-1).tolist()))
+    return T.reshape(6)
+
+
+def check_heat_maps(maps, n_frames, device):
+    """The maps of one draw_heatmaps call -> a view [N, C, h, w] of them (never a copy): a CUDA float32 tensor [N, C, h, w] ([C, h, w]:
+    one frame) on `device` with 1..32 channels and any non-negative strides."""
+    if not isinstance(maps, torch.Tensor):
+        raise _lib.CenterposeHipError("maps must be a CUDA float32 tensor [N, C, h, w] (got %s): there is no CPU fallback" % type(maps).__name__)
+    maps = maps.unsqueeze(0) if maps.dim() == 3 else maps
+    if maps.dim() != 4 or maps.shape[2] < 1 or maps.shape[3] < 1:
+        raise _lib.CenterposeHipError("maps must be [N, C, h, w] (or [C, h, w] for one frame) with h, w >= 1, got shape %s" % (tuple(maps.shape),))
+    if not maps.is_cuda:
+        raise _lib.CenterposeHipError("maps on %s: they must be on the model's GPU; there is no CPU fallback" % maps.device)
+    device = device() if callable(device) else device
+    if maps.device != device:
+        raise _lib.CenterposeHipError("maps on %s, the model is on %s" % (maps.device, device))
+    if maps.dtype != torch.float32:
+        raise _lib.CenterposeHipError("maps must be float32 (got %s)" % maps.dtype)
+    if maps.shape[0] != n_frames:
+        raise _lib.CenterposeHipError("maps hold %d images for %d frames" % (maps.shape[0], n_frames))
+    if not 1 <= maps.shape[1] <= MAX_HEAT_CHANNELS:
+        raise _lib.CenterposeHipError("%d map channels outside 1..%d" % (maps.shape[1], MAX_HEAT_CHANNELS))
+    return maps.detach()
+
+
+def heat_table(frames, yuv, metas, geometry, h, w):
+    """The identity table of `frames` with the frame -> map matrix of each in its `mi` field (free in an identity table).  metas: one per
+    frame, each with c, s, out_height, out_width equal to the maps' (h, w); geometry: (height, width) -> (new_h, new_w)."""
+    metas = list(metas)
+    if len(metas) != len(frames):
+        raise _lib.CenterposeHipError("metas hold %d entries for %d frames" % (len(metas), len(frames)))
+    table = identity_table(frames, yuv)
+    for d, meta in zip(table, metas):
+        if (int(meta["out_height"]), int(meta["out_width"])) != (h, w):
+            raise _lib.CenterposeHipError("a meta of a %d x %d map with maps of %d x %d: metas and maps come from one pre_process_batch call"
+                                          % (meta["out_height"], meta["out_width"], h, w))
+        new_h, new_w = geometry(int(d["H"]), int(d["W"]))
+        d["mi"] = heat_transform(meta, int(d["H"]), int(d["W"]), new_h, new_w)
+    return table
+
+
+def draw_heat(io, frames, maps, metas, geometry, color, matrix, style):
+    """cp_draw_heat_frames_u8 / cp_draw_heat_yuv_frames_u8 for checked frames and checked maps [N, C, h, w]: one table upload through `io`,
+    two launches in the current stream.  The maps go in by pointer and their four element strides."""
+    yuv = color in YUV_COLORS
+    style = HeatmapStyle() if style is None else style
+    if not isinstance(style, HeatmapStyle):
+        raise _lib.CenterposeHipError("style is a HeatmapStyle (got %s)" % type(style).__name__)
+    N, C, h, w = (int(v) for v in maps.shape)
+    rec = style.struct(C)
+    table = heat_table(frames, yuv, metas, geometry, h, w)
+    if N == 0:
+        return
+    L = _lib.lib()
+    L.cp_draw_heat_scratch_bytes.restype = ctypes.c_size_t
+    nbytes = int(L.cp_draw_heat_scratch_bytes(N, h, w))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=maps.device)
+    table_dev, = io.upload_table([table])
+    vp, ll = ctypes.c_void_p, ctypes.c_longlong
+    name = "cp_draw_heat_yuv_frames_u8" if yuv else "cp_draw_heat_frames_u8"
+    rc = getattr(L, name)(vp(table_dev.data_ptr()), table.ctypes.data_as(vp), N, vp(maps.data_ptr()), *(ll(int(s)) for s in maps.stride()), C, h, w,
+                          rec.ctypes.data_as(vp), *((HEAT_MATRIX_IDS[matrix],) if yuv else ()), vp(scratch.data_ptr()), ctypes.c_size_t(nbytes),
+                          _lib.stream())
     _lib.check(rc, name)

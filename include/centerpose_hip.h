@@ -579,6 +579,52 @@ int cp_draw_overlay_frames_host(const void* table_host, int N, const float* rows
 int cp_draw_overlay_yuv_frames_host(const void* table_host, int N, const float* rows, int M, float vis_thresh, const void* style,
                                     const int* row_ids, const void* id_palette, const void* overlay);
 
+/* ---- heat maps blended over device frames, in place: the debug views pred_hm / pred_hmhp (draw_heatmaps) ----------------------------------
+ * What the reference's MultiPoseDetector.debug shows: the centre heat map or the 17 joint heat maps as a colour map (Debugger.gen_colormap /
+ * gen_colormap_hp) blended over the picture (add_blend_img).  Every pixel of every frame is read and written.  The rule is
+ * csrc/draw_heat_arith.h:
+ *   colour map, per image and map cell: m_k = max over c < C of (v_c * palette[c][k]) for k in B, G, R -- one float32 multiply per term,
+ *     from 0 and compared with '>', so a NaN never wins and negatives give 0 -- and cm_k = min(255, (int)m_k); with invert palette[c][k]
+ *     is replaced by 255 - palette[c][k] and cm_k by 255 - cm_k.  Stored as uint8 [N, h, w, 4] in the scratch.
+ *   position, per frame pixel (x, y), in double, with the frame -> map matrix T = the `mi` field of the frame's descriptor row (row major,
+ *     finite): mx = T[0] x + T[1] y + T[2] left to right, clamped to [0, w - 1], X = (long long)(mx * 256.0 + 0.5), ix = X >> 8,
+ *     fx = X & 255, ix1 = min(ix + 1, w - 1); my from T[3..5] and h alike.  Cell (i, j) sits AT map coordinate (i, j); outside the map
+ *     the border repeats.
+ *   sample, per component: t0 = a (256 - fx) + b fx on row iy, t1 on row iy1, f = (t0 (256 - fy) + t1 fy + 32768) >> 16.
+ *   blend: p' = (p (256 - opacity) + f opacity + 128) >> 8 on the three colour bytes; a fourth channel and padding keep their bytes.
+ *   YUV frames (8-bit 4:2:0): f = (B, G, R) goes to (Y, U, V) by the limited-range forward form `matrix` (0: BT.601 Y = ((66 R + 129 G +
+ *     25 B + 128) >> 8) + 16, ...; 1: BT.709), what cp_bgr_to_yuv_host computes; luma per pixel, a chroma sample with the (U, V) of the
+ *     component-wise rounded mean (sum + (n >> 1)) / n of the fore colours of its n in {1, 2, 4} in-frame pixels.
+ * maps: DEVICE float32, element (n, c, i, j) at maps[n s0 + c s1 + i s2 + j s3], any non-negative element strides; never copied.
+ * style: HOST; `channels` palette entries (C..32) of (B, G, R), for the YUV form too.  scratch: DEVICE, 16-byte aligned,
+ *   cp_draw_heat_scratch_bytes(N, h, w) bytes (0 when any argument is 0).
+ * Two launches on `stream`: draw_heat_colormap_kernel (a thread per cell), draw_heat_blend_kernel<bgr_packed|bgr|yuv> -- <bgr_packed> when
+ *   every frame of the call has pix_stride 3 and channel offsets (0,1,2) or (2,1,0): four pixels per thread as three aligned dwords, the
+ *   ragged ends of a row byte-wise; otherwise <bgr>, a pixel per thread byte-wise; bit-identical.  cp_last_kernel() names the one that ran.
+ * Checked before anything is launched: N in 0..65535 (0 succeeds and launches nothing), C in 1..32, channels in C..32, opacity in 1..256,
+ *   invert 0 / 1, matrix 0 / 1, h and w in 1..16384, N h w <= 2^30, non-negative strides, non-null pointers, the scratch, the frames as for
+ *   cp_draw_rows_*, a finite T per frame.
+ * cp_draw_heat_frames_host / cp_draw_heat_yuv_frames_host: HOST only -- sequential painters over HOST maps, same statements, same checks.
+ *   What the device result is pinned to, byte for byte. */
+typedef struct cp_draw_heat_style {     /* 140 bytes */
+    int channels;
+    int opacity;
+    int invert;
+    unsigned char palette[32][4];
+} cp_draw_heat_style;
+int cp_sizeof_draw_heat_style(void);
+size_t cp_draw_heat_scratch_bytes(int N, int h, int w);
+int cp_bgr_to_yuv_host(const unsigned char* bgr, long long n, int matrix, unsigned char* yuv);
+int cp_draw_heat_frames_u8(const void* table, const void* table_host, int N, const float* maps, long long s0, long long s1, long long s2,
+                           long long s3, int C, int h, int w, const void* style, void* scratch, size_t scratch_bytes, void* stream);
+int cp_draw_heat_yuv_frames_u8(const void* table, const void* table_host, int N, const float* maps, long long s0, long long s1, long long s2,
+                               long long s3, int C, int h, int w, const void* style, int matrix, void* scratch, size_t scratch_bytes,
+                               void* stream);
+int cp_draw_heat_frames_host(const void* table_host, int N, const float* maps, long long s0, long long s1, long long s2, long long s3, int C,
+                             int h, int w, const void* style);
+int cp_draw_heat_yuv_frames_host(const void* table_host, int N, const float* maps, long long s0, long long s1, long long s2, long long s3,
+                                 int C, int h, int w, const void* style, int matrix);
+
 /* ---- draw tracks onto device frames, in place: box, label bar, label (draw_tracks / run_batch(draw="tracks")) --------------------------
  * What the reference's draw_bboxes puts on the picture per track, by this library's own integer rule (csrc/draw_text_arith.h) and its
  * own 5 x 7 font.  Frame n paints items[n][0 .. counts[n] - 1] of items[N][Kmax].  With box thickness T (0..64), font scale s (0..8,
