@@ -97,6 +97,10 @@ class PlanBuilder(nets.Graph):
         self.fuse_heads = os.environ.get("CP_FUSE_HEADS", "1") != "0"      # 3x3 + 1x1 of a head branch in one launch
         self._pool_cache = {}
         self.outputs = None
+        self.bn_eps = ops.BN_EPS        # the eps of every BatchNorm this graph folds (Engine sets nets.PRNET_BN_EPS for arch "prnet")
+
+    def fold_bn(self, cout, bn=None, bias=None, device=None):
+        return ops.fold_bn(cout, bn, bias, device, eps=self.bn_eps)
 
     @property
     def bytes_alloc(self):
@@ -143,7 +147,7 @@ class PlanBuilder(nets.Graph):
     @staticmethod
     def act_code(relu):
         return {False: ops.ACT_NONE, None: ops.ACT_NONE, True: ops.ACT_RELU, "relu": ops.ACT_RELU, "hswish": ops.ACT_HSWISH,
-                "hsigmoid": ops.ACT_HSIGMOID}[relu]
+                "hsigmoid": ops.ACT_HSIGMOID, "sigmoid": ops.ACT_SIGMOID}[relu]
 
     def w(self, key):
         hit = self.const_cache.get(("w", key))
@@ -224,12 +228,12 @@ class PlanBuilder(nets.Graph):
         if stem and k == 7 and pad == 3 and co in (16, 64) and res is None and bn and relu in (True, False):
             # dedicated 7x7 stem kernel (NCHW 3-channel input window staged once in LDS)
             wp7 = ops.pack_stem7_weight(self.w(conv + ".weight"))
-            sc7, sh7 = ops.fold_bn(co, self.bn(bn), self.w(conv + ".bias") if bias else None, self.dev)
+            sc7, sh7 = self.fold_bn(co, self.bn(bn), self.w(conv + ".bias") if bias else None, self.dev)
             self.add("conv", conv, 2 * Ho * Wo * co * 3 * 49, ops.stem7x7_launch(xs[0].t, wp7, sc7, sh7, out.t, stride, relu))
             return out
         w = self.w(conv + ".weight")
         wp = ops.pack_conv_weight(w if stem else self.expand_in(w, xs), stem=stem)
-        sc, sh = ops.fold_bn(co, self.bn(bn) if bn else None, self.w(conv + ".bias") if bias else None, self.dev)
+        sc, sh = self.fold_bn(co, self.bn(bn) if bn else None, self.w(conv + ".bias") if bias else None, self.dev)
         srcs = [a.t for a in xs]
         rt = res.t if res is not None else None
         ci = sum(a.C for a in xs)
@@ -262,7 +266,7 @@ class PlanBuilder(nets.Graph):
         recs, flops = [], 0
         for (x, conv, bn, co, relu, res), out in zip(members, outs):
             wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
-            sc, sh = ops.fold_bn(co, self.bn(bn), None, self.dev)
+            sc, sh = self.fold_bn(co, self.bn(bn), None, self.dev)
             recs.append(dict(x=x.t, wp=wp, u24=self.wino_weight("wino24", conv, wp, x.t.shape[3], co), scale=sc, shift=sh, out=out.t,
                              cout=out.t.shape[3], act=self.act_code(relu), res=res.t if res is not None else None))
             flops += 2 * x.H * x.W * co * x.C * 9
@@ -292,7 +296,7 @@ class PlanBuilder(nets.Graph):
             recs, flops = [], 0
             for (x, conv, bn, co, k, stride, pad, relu), out in zip(chunk, couts):
                 wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
-                sc, sh = ops.fold_bn(co, self.bn(bn), None, self.dev)
+                sc, sh = self.fold_bn(co, self.bn(bn), None, self.dev)
                 ldw = ops.round_up(wp.shape[0], 64)
                 recs.append(dict(x=x.t, wp=ops.pad_rows(wp, ldw), scale=ops.pad_vec(sc, ldw), shift=ops.pad_vec(sh, ldw), out=out.t,
                                  cout=out.t.shape[3], k=k, stride=stride, pad=pad, act=self.act_code(relu)))
@@ -317,11 +321,11 @@ class PlanBuilder(nets.Graph):
     def emit_dcn(self, x, conv, bn, co):
         om = self.buf(x.H, x.W, 32)
         wom = ops.pack_conv_weight(self.expand_in(self.w(conv + ".conv_offset_mask.weight"), [x]))     # [9C, 32]
-        som, hom = ops.fold_bn(27, None, self.w(conv + ".conv_offset_mask.bias"), self.dev)
+        som, hom = self.fold_bn(27, None, self.w(conv + ".conv_offset_mask.bias"), self.dev)
         som[27:] = 0.0   # pad channels are written as exact zeros
         out = self.buf(x.H, x.W, co)
         wp = ops.pack_conv_weight(self.expand_in(self.w(conv + ".weight"), [x]))
-        sc, sh = ops.fold_bn(co, self.bn(bn), self.w(conv + ".bias"), self.dev)
+        sc, sh = self.fold_bn(co, self.bn(bn), self.w(conv + ".bias"), self.dev)
         uom = self.wino(wom, x.t.shape[3], 32, conv + ".conv_offset_mask", hw=(x.H, x.W))
         self.add_conv3x3(conv + ".conv_offset_mask", 2 * x.H * x.W * 27 * x.C * 9, x.t, wom, uom, som, hom, om.t, 32, ops.ACT_NONE)
         flops = 2 * x.H * x.W * co * x.C * 9
@@ -348,7 +352,7 @@ class PlanBuilder(nets.Graph):
         Ho, Wo = (x.H + 2 * (k // 2) - k) // stride + 1, (x.W + 2 * (k // 2) - k) // stride + 1
         out = self.buf(Ho, Wo, x.C, x.split)
         g, b, mean, var = self.bn(bn)
-        scale = g / torch.sqrt(var + ops.BN_EPS)
+        scale = g / torch.sqrt(var + self.bn_eps)
         shift = b - mean * scale
         wk = ops.pack_dw_weight(self.w(conv + ".weight"))                       # [k*k, C] over the logical channels
         wkp = torch.stack([self.expand_vec(row, x) for row in wk], 0).contiguous()
@@ -372,6 +376,38 @@ class PlanBuilder(nets.Graph):
         self.outputs = [o]
         return Act(1, 1, x.C, o.view(self.B, 1, 1, x.C))
 
+    def emit_conv_same(self, xs, conv, bn, co, k, stride, relu, res=None, stem=False, transposed=False, bn_scale_only=False,
+                       add_identity=False, nchw_out=False):
+        """PRNet's "same" convolutions on the generic implicit-GEMM launch: the output size is given (H / stride), the padding before
+        is max(k - stride, 0) // 2 (a transposed stride-1 layer: k // 2, with the kernel flipped and in / out swapped at plan time), and the
+        taps behind the map are zero-filled by the gather.  Outputs of fewer than 16 channels are whole 16-channel maps whose padding
+        is WRITTEN as zeros (zero weight rows, zero scale and shift): the pool re-uses buffers."""
+        x = xs[0]
+        Ho, Wo = x.H // stride, x.W // stride
+        w = self.w(conv + ".weight")
+        if transposed:
+            w = w.permute(1, 0, 2, 3).flip(2, 3)
+        pad = k // 2 if transposed else max(k - stride, 0) // 2
+        if add_identity:                                                # [W3 | I] over the sources [h, x]: BN acts on conv(h) + x
+            eye = torch.eye(co, dtype=w.dtype, device=w.device).view(co, co, 1, 1)
+            w = torch.cat([w, eye], 1)
+        wp = ops.pack_conv_weight((w if stem else self.expand_in(w, xs)).contiguous(), stem=stem)
+        sc, sh = self.fold_bn(co, self.bn(bn) if bn else None, None, self.dev)
+        if bn_scale_only:
+            sh = torch.zeros_like(sh)
+        flops = 2 * Ho * Wo * co * x.C * k * k
+        if nchw_out:
+            o = torch.empty((self.B, co, Ho, Wo), dtype=torch.float32, device=self.dev)
+            self.add("conv", conv, flops, ops.conv2d_launch([a.t for a in xs], wp, sc, sh, o, kh=k, kw=k, stride=stride, pad_yx=(pad, pad),
+                                                            Ho=Ho, Wo=Wo, cout=co, act=self.act_code(relu), out_nchw=True))
+            self.outputs = [o]
+            return Act(Ho, Wo, co)
+        out = self.buf(Ho, Wo, co)
+        self.add("conv", conv, flops,
+                 ops.conv2d_launch([a.t for a in xs], wp, sc, sh, out.t, kh=k, kw=k, stride=stride, pad_yx=(pad, pad), Ho=Ho, Wo=Wo,
+                                   cout=out.t.shape[3], act=self.act_code(relu), res=res.t if res is not None else None, in_nchw=stem))
+        return out
+
     def emit_scale_add(self, x, se, add):
         out = self.buf(x.H, x.W, x.C)
         self.add("se", "se.scale", 0, ops.scale_add_launch(x.t, se.t, add.t if add is not None else None, out.t))
@@ -392,7 +428,7 @@ class PlanBuilder(nets.Graph):
     def emit_deconv4(self, x, wname, bn, co):
         out = self.buf(x.H * 2, x.W * 2, co)
         w = self.w(wname + ".weight")
-        sc, sh = ops.fold_bn(co, self.bn(bn), None, self.dev)
+        sc, sh = self.fold_bn(co, self.bn(bn), None, self.dev)
         H, W = x.H, x.W
         # the four sub-pixel 2x2 convolutions in ONE launch (sub g = py*2+px): 4x the blocks - a 2048 -> 256 deconv at
         # 16x16 is otherwise 4 x 128 blocks of 512 k-steps each on 256 CUs
@@ -435,7 +471,7 @@ class PlanBuilder(nets.Graph):
         mid = self.buf(H, W, hc if per_head else 6 * hc)
         if not per_head:
             wp3 = ops.pack_conv_weight(self.expand_in(torch.cat([self.w("%s.%s.0.weight" % (p, h)) for h, _ in nets.HEADS], 0), [feat]))
-            sc3, sh3 = ops.fold_bn(6 * hc, None, torch.cat([self.w("%s.%s.0.bias" % (p, h)) for h, _ in nets.HEADS], 0), self.dev)
+            sc3, sh3 = self.fold_bn(6 * hc, None, torch.cat([self.w("%s.%s.0.bias" % (p, h)) for h, _ in nets.HEADS], 0), self.dev)
             self.add_conv3x3(p + ".*.0", 2 * H * W * 6 * hc * feat.C * 9, ft, wp3, self.wino(wp3, ft.shape[3], 6 * hc, p + ".*.0"), sc3, sh3,
                              mid.t, 6 * hc, ops.ACT_RELU, splitc=False)
         for i, (h, n) in enumerate(nets.HEADS):
@@ -444,12 +480,12 @@ class PlanBuilder(nets.Graph):
                 continue
             o = torch.empty((self.B, n, H, W), dtype=torch.float32, device=self.dev)
             wp = ops.pack_conv_weight(self.w("%s.%s.2.weight" % (p, h)))
-            sc, sh = ops.fold_bn(n, None, self.w("%s.%s.2.bias" % (p, h)), self.dev)
+            sc, sh = self.fold_bn(n, None, self.w("%s.%s.2.bias" % (p, h)), self.dev)
             act = ops.ACT_SIGMOID if h in self.sigmoid_heads else ops.ACT_NONE
             if per_head:
                 key = "%s.%s.0" % (p, h)
                 wp3h = ops.pack_conv_weight(self.expand_in(self.w(key + ".weight"), [feat]))
-                sc3h, sh3h = ops.fold_bn(hc, None, self.w(key + ".bias"), self.dev)
+                sc3h, sh3h = self.fold_bn(hc, None, self.w(key + ".bias"), self.dev)
                 fused_ok = self.fuse_heads and ops.head3x3_1x1_eligible(ft, hc, n)
                 # the fused launch picks its own transform below; a head that runs as two launches may take the F(2x4) kernel (res_50: 256 -> 64)
                 u3h = self.wino(wp3h, ft.shape[3], hc, key, hw=None if fused_ok else (H, W))
@@ -582,6 +618,9 @@ class Engine:
         if nets.canonical_arch(arch) == "reid" and (decode_k or dets_only or flip_test or flip_dets_only):
             raise ValueError("arch 'reid' has no keypoint heads: decode_k, dets_only, flip_test and flip_dets_only do not apply "
                              "(its plan returns [features], a [batch, %d] tensor)" % nets.REID_DIM)
+        if nets.canonical_arch(arch) == "prnet" and (decode_k or dets_only or flip_test or flip_dets_only):
+            raise ValueError("arch 'prnet' has no keypoint heads: decode_k, dets_only, flip_test and flip_dets_only do not apply "
+                             "(its plan returns [position map], a [batch, 3, H, W] tensor)")
         if flip_dets_only:
             # detections-only under the flip test: its own keyword (flip_test=True with dets_only=True keeps refusing below)
             if flip_test or dets_only:
@@ -618,6 +657,8 @@ class Engine:
         with torch.cuda.device(self.device):
             self.input = torch.zeros((batch, 3, height, width), dtype=torch.float32, device=self.device)
             pb = PlanBuilder(sd, batch, self.device, sigmoid_heads, const_cache, dets_only=bool(dets_only or flip_dets_only))
+            if self.arch == "prnet":
+                pb.bn_eps = nets.PRNET_BN_EPS
             pb.network(self.arch, Act(height, width, 3, self.input), head_conv)
         self.launches = pb.launches
         self.emission = pb.launches    # the list in the order of the reference's forward(); `launches` may later be re-ordered by the schedule

@@ -16,6 +16,8 @@ Structure follows the reference modules (they are *not* imported):
   resdcn_N lib/models/backbones/resnet_dcn.py     BasicBlock :34-63, Bottleneck :66-103, PoseResNet :130-276 (N = 18 / 34 / 50 / 101)
   head     lib/models/heads/keypoint.py:14-42
   reid     demo/tracking/model.py                 BasicBlock :6-38, make_layers :40-47, Net :49-93 (the DeepSort re-id net: no keypoint head)
+  prnet    demo/face/resfcn256.py                 padding_same_conv2d :4-13, resBlock :15-47, upBlock :50-73, PRNet :75-148 (the 3-D
+           face position-map net: no keypoint head, BatchNorm eps 1e-3)
 """
 from collections import OrderedDict
 
@@ -24,6 +26,7 @@ HEADS = (("hm", 1), ("wh", 2), ("hps", 34), ("reg", 2), ("hm_hp", 17), ("hp_offs
 ARCH_HEAD = {"dla_34": (64, 256), "res_50": (256, 64), "hrnet": (32, 64), "mobilenetv3": (24, 256), "shufflenetV2": (256, 256),
              "resdcn_18": (64, 64), "resdcn_34": (64, 64), "resdcn_50": (64, 64), "resdcn_101": (64, 64)}
 REID_INPUT, REID_DIM = (128, 64), 512                             # demo/tracking/model.py:52, :69
+PRNET_INPUT, PRNET_BN_EPS = (256, 256), 1e-3                     # demo/face/prnet.py:21-22, resfcn256.py:25
 RESDCN_SPEC = {18: ("basic", [2, 2, 2, 2]), 34: ("basic", [3, 4, 6, 3]), 50: ("bottleneck", [3, 4, 6, 3]),
                101: ("bottleneck", [3, 4, 23, 3])}                       # resnet_dcn.py:270-274
 
@@ -97,6 +100,15 @@ class Graph:
 
     def emit_pool_l2norm(self, x):
         return Act(1, 1, x.C)
+
+    def emit_conv_same(self, xs, conv, bn, co, k, stride, relu, res=None, stem=False, transposed=False, bn_scale_only=False,
+                       add_identity=False, nchw_out=False):
+        """A "same" convolution of PRNet: the output is H / stride x W / stride whatever the kernel, with the zero padding split
+        max(k - stride, 0) // 2 before and the rest after (resfcn256.py:4-13); `transposed`: the weight is a stride-1 ConvTranspose2d's
+        [Ci, Co, k, k] behind a ConstantPad2d, i.e. the flipped kernel padded k // 2 before and the rest after.  bn_scale_only: the
+        launch applies the BN's scale without its shift; add_identity: xs = [h, x] and the launch computes conv(h) + x under the BN;
+        nchw_out: the launch writes the plan's NCHW output."""
+        return Act(xs[0].H // stride, xs[0].W // stride, co)
 
     def emit_dwconv(self, x, conv, bn, k, stride, act):
         return Act((x.H + 2 * (k // 2) - k) // stride + 1, (x.W + 2 * (k // 2) - k) // stride + 1, x.C, split=x.split)
@@ -453,6 +465,74 @@ class Graph:
         assert (x.H, x.W, x.C) == (8, 4, REID_DIM)
         return self.emit_pool_l2norm(x)
 
+    # ---- PRNet: the 3-D face position-map net, no keypoint head, un-prefixed keys ------------------------
+    def _pr_conv(self, xs, name, bn, co, k, stride=1, relu=False, **kw):
+        """conv (no bias) [+ BN `bn`] of a PRNet block through `emit_conv_same`; `name` is the parameter's full prefix."""
+        xs = xs if isinstance(xs, (list, tuple)) else [xs]
+        ci = xs[0].C
+        self.spec[name + ".weight"] = (ci, co, k, k) if kw.get("transposed") else (co, ci, k, k)
+        if bn:
+            self.p_bn(bn, co)
+        out = self.emit_conv_same(xs, name, bn, co, k, stride, relu, **kw)
+        self.flops += 2 * out.H * out.W * co * ci * k * k
+        return out
+
+    def _pr_res(self, x, p, co, stride):
+        """resBlock (resfcn256.py:15-47): ReLU(BN(shortcut(x) + main(x))), main = 1x1 + BN + ReLU, 4x4 / stride + BN + ReLU, 1x1.  The
+        kernels' epilogue is act(acc * scale + shift + res), so the block's BN goes into the last 1x1: with a shortcut convolution
+        that launch runs first with the BN's scale and no shift and is the residual; with the identity shortcut the last 1x1 is a
+        two-source launch over [h, x] with the weights [W3 | I].  Keys in the module's order: shortcut, main, activate; a stride-1
+        4x4 sits behind a ConstantPad2d, which moves the indices of what follows by one."""
+        half, m = co // 2, p + ".main."
+        c2, c3 = (3, 6) if stride == 2 else (4, 7)
+        act_bn = p + ".activate.0"
+        sc = None
+        if x.C != co:
+            self.spec[p + ".shortcut.weight"] = (co, x.C, 1, 1)
+        h = self._pr_conv(x, m + "0", m + "1", half, 1, relu=True)
+        h = self._pr_conv(h, m + str(c2), m + str(c2 + 1), half, 4, stride, relu=True)
+        self.spec[m + str(c3) + ".weight"] = (co, half, 1, 1)
+        self.p_bn(act_bn, co)
+        if x.C != co:
+            sc = self.emit_conv_same([x], p + ".shortcut", act_bn, co, 1, stride, False, bn_scale_only=True)
+            self.flops += 2 * sc.H * sc.W * co * x.C
+            out = self.emit_conv_same([h], m + str(c3), act_bn, co, 1, 1, True, res=sc)
+        else:
+            out = self.emit_conv_same([h, x], m + str(c3), act_bn, co, 1, 1, True, add_identity=True)
+        self.flops += 2 * out.H * out.W * co * half
+        return out
+
+    def _pr_up(self, x, p, co, conv_num):
+        """upBlock (resfcn256.py:50-73): ConvTranspose2d(k4, s2, p1) + BN + ReLU, then conv_num x [pad (2,1,2,1), ConvTranspose2d(k4, s1,
+        p3) + BN + ReLU]."""
+        m = p + ".main."
+        self.spec[m + "0.weight"] = (x.C, co, 4, 4)
+        self.p_bn(m + "1", co)
+        x_in = x
+        x = self.emit_deconv4(x, m + "0", m + "1", co)
+        self.flops += 2 * x_in.H * x_in.W * x_in.C * co * 16
+        for i in range(conv_num):
+            x = self._pr_conv(x, m + str(4 * i + 4), m + str(4 * i + 5), co, 4, relu=True, transposed=True)
+        return x
+
+    def prnet(self, x):
+        """PRNet(3, 3).forward, demo/face/resfcn256.py:127-148: a 4x4 "same" stem, ten resBlocks down to H / 32, a stride-1 transposed
+        centre, five upBlocks back to H and three stride-1 transposed convolutions 16 -> 3 -> 3 -> 3, the last under a sigmoid.  Every
+        BatchNorm has eps 1e-3.  H and W are multiples of 32 (the module is built for 256 x 256; its padding does not depend on the
+        size)."""
+        if x.H % 32 or x.W % 32 or x.H < 32 or x.W < 32:
+            raise ValueError("arch 'prnet' takes inputs whose sides are multiples of 32 (got %d x %d)" % (x.H, x.W))
+        size = 16
+        x = self._pr_conv(x, "input_conv.1", "input_conv.2", size, 4, relu=True, stem=True)
+        for i, (mult, stride) in enumerate([(2, 2), (2, 1), (4, 2), (4, 1), (8, 2), (8, 1), (16, 2), (16, 1), (32, 2), (32, 1)], start=1):
+            x = self._pr_res(x, "down_conv_%d" % i, size * mult, stride)
+        x = self._pr_conv(x, "center_conv.1", "center_conv.2", size * 32, 4, relu=True, transposed=True)
+        for i, mult, n in ((5, 16, 2), (4, 8, 2), (3, 4, 2), (2, 2, 1), (1, 1, 1)):
+            x = self._pr_up(x, "up_conv_%d" % i, size * mult, n)
+        x = self._pr_conv(x, "output_conv.1", "output_conv.2", 3, 4, relu=True, transposed=True)
+        x = self._pr_conv(x, "output_conv.5", "output_conv.6", 3, 4, relu=True, transposed=True)
+        return self._pr_conv(x, "output_conv.9", "output_conv.10", 3, 4, relu="sigmoid", transposed=True, nchw_out=True)
+
     # ---- head --------------------------------------------------------------------------------
     def head(self, feat, hc, p="head_model"):
         for h, n in HEADS:
@@ -465,6 +545,8 @@ class Graph:
         base = canonical_arch(arch)
         if base == "reid":                                            # no keypoint head: the plan ends in the embedding
             return self.reid(x)
+        if base == "prnet":                                           # no keypoint head: the plan ends in the position map
+            return self.prnet(x)
         inter, hc = ARCH_HEAD[base]
         if base.startswith("resdcn_"):
             feat = self.resdcn(x, int(base.split("_")[1]))
@@ -494,8 +576,10 @@ def canonical_arch(arch):
             return "resdcn_%d" % int(n)
     if a == "reid":                                              # demo/tracking/model.py Net(reid=True): not a cfg.MODEL.NAME
         return "reid"
+    if a == "prnet":                                             # demo/face/resfcn256.py PRNet(3, 3): not a cfg.MODEL.NAME
+        return "prnet"
     raise ValueError("unsupported arch %r (the MI355X hot path covers dla_34, res_50, hrnet, mobilenetv3, shufflenetV2, "
-                     "resdcn_18/34/50/101 and the re-id net reid)" % arch)
+                     "resdcn_18/34/50/101 and the re-id net reid; also the face position-map net prnet)" % arch)
 
 
 _HEAD_NAMES = tuple(h for h, _ in HEADS)
@@ -522,8 +606,8 @@ def reference_key(arch, k):
 
 def param_spec(arch, H=None, W=None, head_conv=None, internal=False):
     """OrderedDict name -> shape of the reference checkpoint for `arch`, plus algorithmic FLOPs/image.  Names are the
-    reference's (`reference_key`) unless `internal`.  H, W default to 512 x 512 (reid: its fixed 128 x 64 crop)."""
-    dh, dw = REID_INPUT if canonical_arch(arch) == "reid" else (512, 512)
+    reference's (`reference_key`) unless `internal`.  H, W default to 512 x 512 (reid: its fixed 128 x 64 crop; prnet: 256 x 256)."""
+    dh, dw = {"reid": REID_INPUT, "prnet": PRNET_INPUT}.get(canonical_arch(arch), (512, 512))
     H, W = dh if H is None else H, dw if W is None else W
     g = Graph()
     g.network(arch, Act(H, W, 3), head_conv)

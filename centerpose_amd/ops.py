@@ -12,7 +12,7 @@ import torch
 from . import _lib
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4
-BN_EPS = 1e-5  # nn.BatchNorm2d default (reference never overrides it)
+BN_EPS = 1e-5  # nn.BatchNorm2d default (the detector's and the re-id net's; PRNet's is nets.PRNET_BN_EPS, a property of its graph)
 
 
 class ConvDesc(ctypes.Structure):
@@ -178,11 +178,11 @@ def pack_conv_weight(w, stem=False):
     return pad_rows(wp.float(), ldw_for(Co))
 
 
-def fold_bn(cout, bn=None, bias=None, device=None):
-    """(scale, shift) so that y = conv*scale + shift == BN(conv + bias)  (eval mode)."""
+def fold_bn(cout, bn=None, bias=None, device=None, eps=None):
+    """(scale, shift) so that y = conv*scale + shift == BN(conv + bias)  (eval mode).  eps: the BatchNorm's own (default BN_EPS)."""
     if bn is not None:
         g, b, mean, var = bn
-        scale = g / torch.sqrt(var + BN_EPS)
+        scale = g / torch.sqrt(var + (BN_EPS if eps is None else eps))
         shift = b - mean * scale
         if bias is not None:
             shift = shift + bias * scale

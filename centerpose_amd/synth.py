@@ -46,7 +46,10 @@ def _feeds_residual_add(name, arch=""):
 
 # empirical damping of the remaining BN gammas so that activations stay O(1) through depth
 GAMMA_DAMP = {"dla_34": 0.8, "res_50": 0.75, "hrnet": 0.62, "mobilenetv3": 0.8, "shufflenetV2": 0.65,
-              "resdcn_18": 0.85, "resdcn_34": 0.85, "resdcn_50": 0.75, "resdcn_101": 0.75, "reid": 0.85}
+              "resdcn_18": 0.85, "resdcn_34": 0.85, "resdcn_50": 0.75, "resdcn_101": 0.75, "reid": 0.85, "prnet": 0.9}
+# PRNet (demo/face/resfcn256.py) ends in BatchNorm2d(3) + Sigmoid: with the module's own init every output lies in 0.416..0.602.  The
+# last BN's gamma is widened so that the position map spans most of (0, 1), as a trained net's does.
+PRNET_LAST_BN, PRNET_LAST_GAMMA = "output_conv.10", 2.5
 
 HEAD_TARGET = {  # final 1x1 layer: (output std, bias)
     "hm": (3.0, -1.0), "wh": (4.0, 12.0), "hps": (8.0, 0.0), "reg": (0.2, 0.5), "hm_hp": (3.0, -1.5),
@@ -73,6 +76,8 @@ def make_state_dict(arch, seed=317, head_conv=None, H=None, W=None):
         elif len(shp) == 1 and leaf == "weight":                     # BN gamma
             v = r.uniform(0.5, 1.5, shp)
             v = v * (0.3 if _feeds_residual_add(name, arch) else GAMMA_DAMP[arch])
+            if arch == "prnet" and name.startswith(PRNET_LAST_BN):
+                v = v * PRNET_LAST_GAMMA
         elif len(shp) == 1 and "conv_offset_mask" in name:           # offset / mask bias
             v = r.uniform(-1, 1, shp)
             if far % 3 == 0:                                          # some taps sample far outside the map
@@ -92,6 +97,9 @@ def make_state_dict(arch, seed=317, head_conv=None, H=None, W=None):
             v = r.randn(*shp) * (1.7 * math.sqrt(2.0 / (shp[1] * 9)))
         elif "deconv_layers" in name:                                 # ConvTranspose2d [Ci,Co,4,4]
             v = r.randn(*shp) * math.sqrt(2.0 / (shp[0] * 4))
+        elif arch == "prnet" and (name.startswith(("center_conv", "up_conv", "output_conv"))):
+            # ConvTranspose2d [Ci,Co,4,4]: stride 2 (`main.0` of an upBlock) gives every output 4 taps per input channel, stride 1 all 16
+            v = r.randn(*shp) * math.sqrt(2.0 / (shp[0] * (4 if name.endswith("main.0.weight") else 16)))
         else:
             fan = shp[1] * shp[2] * shp[3]
             gain = math.sqrt(2.0 / fan)

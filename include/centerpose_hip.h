@@ -756,6 +756,51 @@ int cp_linear_assignment_host(const double* cost, int rows, int cols, int ld, in
 int cp_track_row_ids(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids, void* stream);
 int cp_track_row_ids_host(const int* slots, const int* slot_ids, int capacity, int S, int q, int M, int* row_ids);
 
+/* ---- 3-D face alignment: similarity crops into the PRNet plan's input, position maps back to the image (face.FaceAligner) -----------
+ * What PRN.process and PRN.get_landmarks do per face on the host (demo/face/prnet.py:61-127), for every candidate of every frame.  The
+ * values are this library's own closed-form statement of that pipeline (csrc/face_arith.h), float32 throughout, not pinned to a
+ * recording of skimage (estimate_transform / warp):
+ *   candidates: cand DEVICE float32 [N,M,56] detection rows (rule.boxes = 0: the box is the min / max of the five face joints, floats
+ *     5..14) or [N,M,5] boxes (x1, y1, x2, y2, score; rule.boxes = 1).  old_size = ((right - left) + bottom - top) / 2,
+ *     size = (int)(old_size * expand), centre (right - (right - left) / 2, bottom - (bottom - top) / 2), x0 = cx - size / 2, y0 alike.
+ *     Selected iff score > vis_thresh (strict; NaN is not), every coordinate read is finite and min_size <= size <= 32768.
+ *   slots: with q = cap / N the first q selected candidates of frame n, in order, take slots n * q + 0, 1, ...
+ *   crop pixel (u, v) samples the frame at (x0 + u * (size / 255), y0 + v * (size / 255)): bilinear over the four neighbours, a neighbour
+ *     outside the frame contributing 0, divided by 255, channels written as R, G, B.
+ *   restore: P = out * 281.6; x = P_x * (size / 255) + x0, y alike, z = P_z * (size / 255).
+ * cp_face_rule (HOST): vis_thresh, expand (in (0, 1024]), min_size (1..32768), boxes.
+ * cp_face_select: one wave per frame -> slots[cap] DEVICE int (n * M + m, or -1), counts[N] DEVICE int (NOT capped at q),
+ *   xform[cap,3] DEVICE float32 (x0, y0, size; zeros for an unused slot).
+ * cp_face_crop_frames_f32 / cp_face_crop_yuv_frames_f32: out DEVICE float32 [cap,3,256,256], every element written; zeros for a slot
+ *   that is unused.  Frames are read in place through the descriptors exactly as by the re-id crops (same tables, same checks, same
+ *   YUV sampler; coef: HOST int[6]).  cp_last_kernel(): face_select_kernel<rows|boxes>, face_crop_kernel<bgr|yuv|surfaces>.
+ * cp_face_restore_f32: net DEVICE float32 [cap,3,256,256] (the plan's output), uv DEVICE int [2,68] (column, then row, of every
+ *   landmark's cell, each in 0..255: the caller's to check) -> pos DEVICE float32 [cap,256,256,3] (NULL: not written) and
+ *   landmarks DEVICE float32 [cap,68,3]; zeros for an unused slot.
+ *   Checked before anything is launched (rc 1, cp_last_error): null pointers, cap in 1..256, 1 <= N <= cap, M >= 0, N * M <= 2^24, the
+ *   rule's ranges, and per frame what the re-id crops check.
+ * cp_face_*_host: HOST only -- sequential twins over host arrays, built from the same statements; same checks (the restore twin also
+ *   refuses a uv entry outside 0..255).  What the device results are pinned to, bit for bit. */
+typedef struct cp_face_rule {       /* 16 bytes */
+    float vis_thresh;
+    float expand;
+    int min_size;
+    int boxes;
+} cp_face_rule;
+int cp_sizeof_face_rule(void);
+int cp_face_select(int N, const float* cand, int M, const void* rule, int cap, int* slots, int* counts, float* xform, void* stream);
+int cp_face_crop_frames_f32(const void* table, const void* table_host, int N, int M, const int* slots, const float* xform, int cap,
+                            float* out, void* stream);
+int cp_face_crop_yuv_frames_f32(const void* table, const void* table_host, int N, const int* coef, int M, const int* slots,
+                                const float* xform, int cap, float* out, void* stream);
+int cp_face_restore_f32(const float* net, const int* slots, const float* xform, int cap, const int* uv, float* pos, float* landmarks,
+                        void* stream);
+int cp_face_select_host(int N, const float* cand, int M, const void* rule, int cap, int* slots, int* counts, float* xform);
+int cp_face_crop_frames_host(const void* table_host, int N, int M, const int* slots, const float* xform, int cap, float* out);
+int cp_face_crop_yuv_frames_host(const void* table_host, int N, const int* coef, int M, const int* slots, const float* xform, int cap,
+                                 float* out);
+int cp_face_restore_host(const float* net, const int* slots, const float* xform, int cap, const int* uv, float* pos, float* landmarks);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
