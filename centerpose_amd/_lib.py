@@ -31,6 +31,18 @@ def lib():
         _lib.cp_last_error.restype = ctypes.c_char_p
         _lib.cp_target_arch.restype = ctypes.c_char_p
         _lib.cp_last_kernel.restype = ctypes.c_char_p
+        # the head-pose stage (csrc/face_pose.hip): size_t crosses the boundary, so these are declared
+        _lib.cp_face_pose_scratch_bytes.restype = c_size_t
+        _lib.cp_face_pose_scratch_bytes.argtypes = [c_int, c_int]
+        pose = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_size_t] + [c_void_p] * 5
+        _lib.cp_face_pose_host.argtypes = pose
+        _lib.cp_face_pose_f32.argtypes = pose + [c_void_p]
+        # the face overlays (csrc/face_draw.hip)
+        _lib.cp_face_draw_scratch_bytes.restype = c_size_t
+        _lib.cp_face_draw_scratch_bytes.argtypes = [c_int]
+        faces = [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p]
+        _lib.cp_face_draw_frames_host.argtypes = _lib.cp_face_draw_yuv_frames_host.argtypes = faces
+        _lib.cp_face_draw_frames_u8.argtypes = _lib.cp_face_draw_yuv_frames_u8.argtypes = [c_void_p] + faces + [c_void_p, c_size_t, c_void_p]
     return _lib
 
 

@@ -37,6 +37,7 @@ from .decode import multi_pose_decode
 from .draw import DRAW_LEFT, DRAW_LIMBS, DRAW_MID, DRAW_OVERLAY, DRAW_RIGHT, DRAW_STYLE, DrawStyle, draw_rows, palette_to_yuv        # noqa: F401
 from .draw import TRACK_ITEM, TRACK_PALETTE, TrackStyle, draw_track_items                                            # noqa: F401
 from .draw import DRAW_HEAT_STYLE, HeatmapStyle, check_heat_maps, draw_heat                                          # noqa: F401
+from .draw import FACE_STYLE, FaceStyle, draw_faces                                                                   # noqa: F401
 from .frames import (FRAME_DESC, PRE_DESC, SURFACE_COLORS, SURFACE_MATRICES, YUV_COLORS, YUV_FRAME_DESC, YUV_MATRICES, FrameIO,      # noqa: F401
                      _check_layout, byte_range, check_drawable, check_rows, frame_geometry, frame_writable, identity_table, is_yuv, yuv_coef,
                      yuv_frame_geometry, yuv_surface_geometry)
@@ -373,7 +374,7 @@ class BaseDetector(object):
         raise NotImplementedError
 
     def run_batch(self, images, dets_only=False, layout="hwc", color="bgr", return_device=False, matrix="bt601", draw=False, embed=None,
-                  track=None, draw_style=None):
+                  track=None, draw_style=None, face=None, face_style=None):
         """N images (HxWx3 uint8 BGR arrays, sizes may differ) -> list of N results, results[n] == run(images[n])["results"].
         One upload of the images and one of every descriptor table / affine of the call; per group of images with equal network input
         shapes and per TEST_SCALES entry a batched pre-process, ONE `process` of the whole group and a batched post-process; one merge
@@ -407,7 +408,15 @@ class BaseDetector(object):
         with their default styles.  The return value is exactly what it is without `draw`; the painting adds no synchronisation and
         one table upload per painting call.
         draw_style (a DrawStyle; needs `draw`): what draw=True / draw="tracks" paint the rows with -- score labels, translucent limbs
-        (DrawStyle(labels=True, limb_opacity=128)); None is the default style, exactly as before.  The return value does not change."""
+        (DrawStyle(labels=True, limb_opacity=128)); None is the default style, exactly as before.  The return value does not change.
+        face=aligner (a face.FaceAligner; device frames only): what the call returns without `face`, as a tuple, with the aligner's
+        FaceResult for the call's own rows appended as its last element -- what aligner.align(images, rows=rows, layout, color, matrix,
+        vis_thresh=TEST.VIS_THRESH, pose=<the aligner has its head-pose tables>) gives, once the rows are in input order and before
+        anything is painted (the crops see clean frames, as for embed=).  Host arrays, or more frames than the aligner's capacity:
+        ValueError, before anything is launched.  Goes with dets_only, return_device, embed, track and draw.
+        face_style (a FaceStyle; needs face=): the faces are painted onto the frames with it, as aligner.draw(images, result, layout,
+        color, matrix, style=face_style) does, after the other painting; the frames must be writable as for draw=True.  The return value
+        does not change."""
         given, io = images, self._io
         if draw_style is not None:
             if not isinstance(draw_style, DrawStyle):
@@ -427,6 +436,21 @@ class BaseDetector(object):
                 raise ValueError("%d frames for an extractor of capacity %d: every frame needs at least one slot" % (len(images), embed.capacity))
             if embed.device != self._model_device():
                 raise _lib.CenterposeHipError("the extractor is on %s, the model is on %s" % (embed.device, self._model_device()))
+        if face_style is not None:
+            if face is None:
+                raise ValueError("face_style= is what the faces of face= are painted with: without `face` there are none")
+            if not isinstance(face_style, FaceStyle):
+                raise ValueError("face_style is a FaceStyle (got %s)" % type(face_style).__name__)
+            _check_layout(layout, color, matrix)
+            check_drawable(color, matrix)
+        if face is not None:
+            if frames is None:
+                raise ValueError("face= takes its crops from frames on the device (CUDA uint8 tensors): host arrays are not read, "
+                                 "there is no CPU fallback")
+            if not 1 <= len(images) <= face.capacity:
+                raise ValueError("%d frames for an aligner of capacity %d: every frame needs at least one slot" % (len(images), face.capacity))
+            if face.device != self._model_device():
+                raise _lib.CenterposeHipError("the aligner is on %s, the model is on %s" % (face.device, self._model_device()))
         if track is not None:
             if embed is None:
                 raise ValueError("track= needs embed=: the tracker matches the extractor's features")
@@ -440,6 +464,12 @@ class BaseDetector(object):
             raise ValueError("draw=%r: False, True or \"tracks\"" % (draw,))
         if draw == "tracks" and track is None:
             raise ValueError("draw=\"tracks\" needs track=: it paints the tracker's identities")
+        if face_style is not None:
+            if face_style.vertices and not face.has_pose_tables:
+                raise ValueError("face_style.vertices needs an aligner built with face_ind=")
+            if face_style.pose_box and not face.has_pose_tables:
+                raise ValueError("face_style.pose_box needs an aligner built with face_ind= and canonical_vertices=")
+            io.check_writable(given, images, color)
         if draw:
             if frames is None and images:
                 raise _lib.CenterposeHipError("draw=True paints frames on the device (CUDA uint8 tensors): host arrays are not painted, "
@@ -457,7 +487,7 @@ class BaseDetector(object):
                 work.append((table, scratch_bytes, inp_h, inp_w))
                 parts += [table, self._inverse_affines(metas)]
         order = [i for idx in groups for i in idx]               # merged row block r belongs to image order[r]
-        if (return_device or draw or embed is not None) and len(groups) > 1:
+        if (return_device or draw or embed is not None or face is not None) and len(groups) > 1:
             parts.append(np.argsort(np.asarray(order, np.int64)).astype(np.int64))       # rides in the one table upload
         staging = io.upload_images(images, offsets, nbytes) if frames is None else None
         parts = io.upload_table(parts)
@@ -476,10 +506,14 @@ class BaseDetector(object):
             merged.append(self.merge_outputs_batch(per_scale))
         rows = merged[0] if len(merged) == 1 else torch.cat(merged, 0)
         ordered = result = None
-        if draw or return_device or embed is not None:
+        if draw or return_device or embed is not None or face is not None:
             ordered = rows if len(groups) == 1 else rows.index_select(0, parts[-1].view(torch.int64))
         if embed is not None:                                    # from the frames as they were given: before anything is painted
             result = embed._embed(frames, ordered.contiguous(), color, matrix, float(self.cfg.TEST.VIS_THRESH))
+        faces = None
+        if face is not None:                                     # likewise before anything is painted
+            faces = face._align(frames, ordered.contiguous(), False, color, matrix, float(self.cfg.TEST.VIS_THRESH), True,
+                                face.has_pose_tables)
         tracks = None
         if track is not None:                                    # before anything is painted, like the crops
             tracks = track.update(ordered, result, [(int(w), int(h)) for h, w in shapes])
@@ -490,13 +524,18 @@ class BaseDetector(object):
             draw_track_items(io, frames, tracks, color, matrix, None)
         elif draw:
             draw_rows(io, frames, ordered, color, matrix, self.cfg.TEST.VIS_THRESH, draw_style)
+        if face_style is not None:                               # after the other painting
+            draw_faces(io, frames, faces, face.face_ind_device, color, matrix, face_style)
+        more = () if embed is None else (result,) if track is None else (result, tracks)
+        if face is not None:
+            more += (faces,)
         if return_device:
-            return ordered if embed is None else (ordered, result) if track is None else (ordered, result, tracks)
+            return (ordered,) + more if more else ordered
         rows = rows.cpu().numpy()                                                               # the one download
         results = [None] * len(images)
         for r, i in enumerate(order):
             results[i] = {1: rows[r].tolist()}
-        return results if embed is None else (results, result) if track is None else (results, result, tracks)
+        return (results,) + more if more else results
 
     def draw_results(self, frames, rows, layout="hwc", color="bgr", matrix="bt601", vis_thresh=None, style=None, row_ids=None,
                      id_palette=None):

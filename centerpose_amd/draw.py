@@ -180,6 +180,74 @@ def draw_rows(io, frames, rows, color, matrix, vis_thresh, style, row_ids=None, 
     _lib.check(rc, name)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the face overlays
+# cp_face_style (include/centerpose_hip.h); colours: landmark, line, vertex, box
+FACE_STYLE = np.dtype([("landmarks", "<i4"), ("vertices", "<i4"), ("pose_box", "<i4"), ("landmark_radius", "<i4"), ("line_radius", "<i4"),
+                       ("box_radius", "<i4"), ("vertex_radius", "<i4"), ("vertex_step", "<i4"), ("colors", "u1", (4, 4))])
+
+
+class FaceStyle:
+    """How FaceAligner.draw paints: the layers `landmarks` (the 68 points and the lines between them: plot_kpt, what the reference's
+    live loop pastes back), `vertices` (every vertex_step-th vertex of face_ind: plot_vertices) and `pose_box` (plot_pose_box), their
+    colours as (B, G, R) as in demo/face/utils/cv_plot.py, radii in 0..3 and vertex_step >= 1."""
+
+    def __init__(self, landmarks=True, vertices=False, pose_box=False, landmark_color=(0, 0, 255), line_color=(255, 255, 255),
+                 vertex_color=(255, 0, 0), box_color=(0, 255, 0), landmark_radius=2, line_radius=1, box_radius=1, vertex_radius=1,
+                 vertex_step=2):
+        self.landmarks, self.vertices, self.pose_box = bool(landmarks), bool(vertices), bool(pose_box)
+        self.colors = [tuple(int(v) for v in c) for c in (landmark_color, line_color, vertex_color, box_color)]
+        self.radii = [int(landmark_radius), int(line_radius), int(box_radius), int(vertex_radius)]
+        self.vertex_step = int(vertex_step)
+        for c in self.colors:
+            if len(c) != 3 or any(not (0 <= v <= 255) for v in c):
+                raise ValueError("a colour is three values in 0..255, got %r" % (c,))
+        for name, r in zip(("landmark_radius", "line_radius", "box_radius", "vertex_radius"), self.radii):
+            if not 0 <= r <= 3:
+                raise ValueError("%s %d outside 0..3" % (name, r))
+        if self.vertex_step < 1:
+            raise ValueError("vertex_step %d below 1" % self.vertex_step)
+
+    def struct(self, matrix=None):
+        """One FACE_STYLE record; `matrix`: the colours as (Y, U, V) for YUV frames."""
+        rec = np.zeros(1, FACE_STYLE)
+        rec["landmarks"], rec["vertices"], rec["pose_box"] = int(self.landmarks), int(self.vertices), int(self.pose_box)
+        rec["landmark_radius"], rec["line_radius"], rec["box_radius"], rec["vertex_radius"] = self.radii
+        rec["vertex_step"] = self.vertex_step
+        rec["colors"][0, :, :3] = np.asarray(self.colors if matrix is None else palette_to_yuv(self.colors, matrix), np.uint8)
+        return rec
+
+
+def draw_faces(io, frames, result, face_ind, color, matrix, style):
+    """cp_face_draw_frames_u8 / cp_face_draw_yuv_frames_u8 for checked frames and a FaceResult on the device: one table upload through
+    `io`, two or three launches in the current stream.  face_ind: the aligner's DEVICE int32 table or None."""
+    yuv = color in YUV_COLORS
+    style = FaceStyle() if style is None else style
+    if not isinstance(style, FaceStyle):
+        raise ValueError("style is a FaceStyle (got %s)" % type(style).__name__)
+    if style.pose_box and result.pose is None:
+        raise ValueError("pose_box=True needs a result with a pose (align(..., pose=True) or estimate_pose)")
+    if style.vertices and (result.pos is None or face_ind is None):
+        raise ValueError("vertices=True needs the position maps (positions=True) and an aligner built with face_ind=")
+    N, cap = len(frames), int(result.slots.shape[0])
+    if not 1 <= N <= cap:
+        raise ValueError("%d frames for a result of capacity %d" % (N, cap))
+    table = identity_table(frames, yuv)
+    rec = style.struct(matrix if yuv else None)
+    L = _lib.lib()
+    nbytes = int(L.cp_face_draw_scratch_bytes(cap))
+    dev = result.slots.device
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    table_dev, = io.upload_table([table])
+    ptr = lambda t: None if t is None else t.data_ptr()
+    pose = result.pose if style.pose_box else None
+    name = "cp_face_draw_yuv_frames_u8" if yuv else "cp_face_draw_frames_u8"
+    rc = getattr(L, name)(table_dev.data_ptr(), table.ctypes.data, N, result.slots.data_ptr(), cap, result.landmarks.data_ptr(),
+                          ptr(pose and pose.box), ptr(pose and pose.valid), ptr(result.pos if style.vertices else None),
+                          ptr(face_ind if style.vertices else None), int(face_ind.shape[0]) if style.vertices else 0, rec.ctypes.data,
+                          scratch.data_ptr(), nbytes, _lib.stream())
+    _lib.check(rc, name)
+
+
 # ---------------------------------------------------------------------------------------------------------------- tracks: boxes and labels
 # cp_draw_track_item / cp_draw_id_palette (include/centerpose_hip.h)
 TRACK_ITEM = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("color", "u1", (4,)), ("text_color", "u1", (4,)),

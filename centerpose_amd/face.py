@@ -11,18 +11,21 @@ The crop is a closed-form statement of the reference's pipeline (csrc/face_arith
 not pinned to a recording of estimate_transform / warp.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
 
 from . import _lib, nets
 from .engine import Engine
-from .frames import FrameIO, check_rows, identity_table, is_yuv, yuv_coef
+from .draw import FaceStyle, draw_faces
+from .frames import FrameIO, _check_layout, check_drawable, check_rows, identity_table, is_yuv, yuv_coef
 from .reid import _holds_host_array
 
 # cp_face_rule (include/centerpose_hip.h)
 FACE_RULE = np.dtype([("vis_thresh", "<f4"), ("expand", "<f4"), ("min_size", "<i4"), ("boxes", "<i4")])
 RES, NKPT, MAX_CAPACITY, MAX_SIZE = 256, 68, 256, 32768
+MIN_VERTICES, MAX_VERTICES = 3, 65536
 
 
 def load_prnet_state_dict(path):
@@ -47,6 +50,59 @@ def check_uv_kpt_ind(uv):
     return np.ascontiguousarray(a.astype(np.int32))
 
 
+def _is_path(x):
+    return isinstance(x, (str, bytes)) or hasattr(x, "__fspath__")
+
+
+def _load_table(x):
+    """An array, or the reference's file of one: text (face_ind.txt) or .npy (canonical_vertices.npy)."""
+    if not _is_path(x):
+        return np.asarray(x)
+    name = os.fsdecode(x)
+    return np.load(name, allow_pickle=False) if name.endswith(".npy") else np.loadtxt(name)
+
+
+def check_pose_tables(face_ind, canonical_vertices):
+    """The two tables of estimate_pose (get_vertices' face_ind, prnet.py:130-140; canonical_vertices, estimate_pose.py:94), arrays or the
+    paths of the reference's files -> (face_ind int32 [V], the canonical cloud centred in float64 [V, 3], float64 [4]: its mean and
+    rms_d1, estimate_pose.py:73,86), or ValueError.  face_ind: V whole numbers in 0..65535 (cells of the flattened 256 x 256 map),
+    3 <= V <= 65536, duplicates and any order allowed; canonical_vertices: finite [V, 3]."""
+    ind, can = _load_table(face_ind), _load_table(canonical_vertices)
+    if ind.ndim != 1 or not MIN_VERTICES <= ind.shape[0] <= MAX_VERTICES:
+        raise ValueError("face_ind must be one row of %d..%d cells (got shape %s)" % (MIN_VERTICES, MAX_VERTICES, tuple(ind.shape)))
+    if ind.dtype.kind not in "iuf" or not np.isfinite(ind.astype(np.float64)).all() or (ind != np.floor(ind)).any():
+        raise ValueError("face_ind must hold whole numbers")
+    if (ind < 0).any() or (ind >= RES * RES).any():
+        raise ValueError("face_ind entries must lie in 0..%d" % (RES * RES - 1))
+    if can.dtype.kind not in "iuf" or can.ndim != 2 or can.shape[1] != 3:
+        raise ValueError("canonical_vertices must be numbers [V, 3] (got shape %s)" % (tuple(can.shape),))
+    if can.shape[0] != ind.shape[0]:
+        raise ValueError("canonical_vertices holds %d vertices for %d entries of face_ind" % (can.shape[0], ind.shape[0]))
+    can = can.astype(np.float64)
+    if not np.isfinite(can).all():
+        raise ValueError("canonical_vertices must be finite")
+    mean = can.mean(axis=0)
+    centred = np.ascontiguousarray(can - mean)
+    rms_d1 = float(np.sqrt(np.mean(np.sum(centred * centred, axis=1))))
+    if not (np.isfinite(rms_d1) and rms_d1 > 0.0):
+        raise ValueError("canonical_vertices must not be one point (rms distance from the mean %r)" % rms_d1)
+    return np.ascontiguousarray(ind.astype(np.int32)), centred, np.asarray([mean[0], mean[1], mean[2], rms_d1], np.float64)
+
+
+class FacePose:
+    """The head pose of every slot (estimate_pose, demo/face/utils/estimate_pose.py:93-99; csrc/face_pose_arith.h), all on the device:
+    P [capacity, 3, 4] float64 -- the affine camera matrix [s R | t] that takes the canonical cloud onto the slot's vertices;
+    angles [capacity, 3] float64 -- matrix2angle's (x, y, z), which the reference calls yaw, pitch, roll;
+    scale [capacity] float64 -- s;
+    box [capacity, 10, 2] int32 -- the ten projected corners of plot_pose_box (cv_plot.py:48-70);
+    valid [capacity] int32 -- 1 iff the slot is used, every vertex and moment is finite and the vertices are not one point.
+    Unused slots and slots with valid == 0 are all zeros."""
+    __slots__ = ("P", "angles", "scale", "box", "valid")
+
+    def __init__(self, P, angles, scale, box, valid):
+        self.P, self.angles, self.scale, self.box, self.valid = P, angles, scale, box, valid
+
+
 class FaceResult:
     """What one `align` call returns, all on the device, ready in the current stream's order:
     pos [capacity, 256, 256, 3] float32 or None (positions=False) -- slot s holds the position map of candidate `slots[s]` in image
@@ -55,11 +111,12 @@ class FaceResult:
     slots [capacity] int32 -- n * M + m of the candidate in slot s, -1 for an unused slot; with q = capacity // N the first q selected
     candidates of frame n, in order, sit in slots n * q + 0, 1, ...;
     counts [N] int32 -- the selected candidates of every frame, NOT capped at q;
-    xform [capacity, 3] float32 -- (x0, y0, size) of every slot's crop square: frame x = x0 + u * size / 255."""
-    __slots__ = ("pos", "landmarks", "slots", "counts", "xform")
+    xform [capacity, 3] float32 -- (x0, y0, size) of every slot's crop square: frame x = x0 + u * size / 255;
+    pose -- a FacePose (align(..., pose=True)) or None."""
+    __slots__ = ("pos", "landmarks", "slots", "counts", "xform", "pose")
 
-    def __init__(self, pos, landmarks, slots, counts, xform):
-        self.pos, self.landmarks, self.slots, self.counts, self.xform = pos, landmarks, slots, counts, xform
+    def __init__(self, pos, landmarks, slots, counts, xform, pose=None):
+        self.pos, self.landmarks, self.slots, self.counts, self.xform, self.pose = pos, landmarks, slots, counts, xform, pose
 
     def vertices(self, face_ind):
         """-> [capacity, len(face_ind), 3]: the map's cells `face_ind` (indices into the flattened 256 x 256 map; get_vertices,
@@ -75,9 +132,11 @@ class FaceAligner:
 
     state_dict: the reference module's own keys (`input_conv.1.weight`, `down_conv_1.main.0.weight`, ...; `load_prnet_state_dict`).
     uv_kpt_ind: [2, 68] integers in 0..255 or the path of the reference's text file; the product ships no reference data.
-    expand / min_size: the crop square has side int(old_size * expand) and is taken iff that is in min_size..32768."""
+    expand / min_size: the crop square has side int(old_size * expand) and is taken iff that is in min_size..32768.
+    face_ind / canonical_vertices: the two tables of the head pose (`check_pose_tables`), both or neither; with them
+    `align(..., pose=True)` and `estimate_pose` are available."""
 
-    def __init__(self, state_dict, uv_kpt_ind, capacity=8, device="cuda", expand=1.6, min_size=1):
+    def __init__(self, state_dict, uv_kpt_ind, capacity=8, device="cuda", expand=1.6, min_size=1, face_ind=None, canonical_vertices=None):
         capacity = int(capacity)
         if not 1 <= capacity <= MAX_CAPACITY:
             raise ValueError("capacity must lie in 1..%d (got %d)" % (MAX_CAPACITY, capacity))
@@ -89,6 +148,10 @@ class FaceAligner:
         if not 0.0 < float(expand) <= 1024.0:
             raise ValueError("expand must lie in (0, 1024] (got %r)" % (expand,))
         uv = load_uv_kpt_ind(uv_kpt_ind) if isinstance(uv_kpt_ind, (str, bytes)) or hasattr(uv_kpt_ind, "__fspath__") else check_uv_kpt_ind(uv_kpt_ind)
+        if (face_ind is None) != (canonical_vertices is None):
+            raise ValueError("the head pose needs face_ind and canonical_vertices together (got only %s)"
+                             % ("face_ind" if canonical_vertices is None else "canonical_vertices"))
+        tables = check_pose_tables(face_ind, canonical_vertices) if face_ind is not None else None
         self.capacity, self.expand, self.min_size = capacity, float(expand), int(min_size)
         self.uv_kpt_ind = uv
         self.engine = Engine("prnet", state_dict, capacity, nets.PRNET_INPUT[0], nets.PRNET_INPUT[1], device=device)
@@ -96,9 +159,26 @@ class FaceAligner:
         self._io = FrameIO(self.device)
         with torch.cuda.device(self.device):
             self._uv = torch.from_numpy(uv).to(self.device)
+            self.face_ind = self._pose_tables = None
+            if tables is not None:
+                self.face_ind = tables[0]
+                scratch = _lib.lib().cp_face_pose_scratch_bytes(capacity, len(tables[0]))
+                # the centred cloud, its mean and rms_d1: uploaded once; the moments' scratch is this aligner's own
+                self._pose_tables = tuple(torch.from_numpy(t).to(self.device) for t in tables) + (
+                    torch.empty((scratch // 8,), dtype=torch.float64, device=self.device),)
             self.engine.capture()      # the one-off capture synchronises: here, not in the first align
 
-    def align(self, frames, rows=None, boxes=None, layout="hwc", color="bgr", matrix="bt601", vis_thresh=0.3, positions=True):
+    @property
+    def face_ind_device(self):
+        """The aligner's face_ind on the device (int32 [V]) or None."""
+        return self._pose_tables[0] if self._pose_tables is not None else None
+
+    @property
+    def has_pose_tables(self):
+        """True iff the aligner was built with face_ind and canonical_vertices: pose=True and estimate_pose are available."""
+        return self._pose_tables is not None
+
+    def align(self, frames, rows=None, boxes=None, layout="hwc", color="bgr", matrix="bt601", vis_thresh=0.3, positions=True, pose=False):
         """Position maps and landmarks of the faces of `frames` -> FaceResult, on the device, in the current stream, no
         synchronisation; the descriptor table is the only upload.
         frames: as for ReidExtractor.embed -- a list of CUDA uint8 tensors or one 4-D tensor (`layout`, `color`, C = 3 or 4), or with a
@@ -106,7 +186,11 @@ class FaceAligner:
         Exactly one of rows / boxes: rows CUDA float32 [N, M, 56] as run_batch(..., return_device=True) returns them (the face box is
         the extent of the five face joints), or boxes CUDA float32 [N, F, 5] = (x1, y1, x2, y2, score) (PRN.process(frame, box) on the
         whole frame).  A candidate gets a face iff its score is > vis_thresh and its square is valid (csrc/face_arith.h).
-        positions=False: the 68 landmarks only; the maps are never written."""
+        positions=False: the 68 landmarks only; the maps are never written.
+        pose=True: `FaceResult.pose` is the head pose of every slot (FacePose), from the plan's output where it lies: with
+        positions=False the maps are still never written.  Needs the aligner's face_ind and canonical_vertices."""
+        if pose and self._pose_tables is None:
+            raise ValueError("pose=True needs a FaceAligner built with face_ind= and canonical_vertices=")
         if (rows is None) == (boxes is None):
             raise ValueError("align takes exactly one of rows= and boxes=")
         if _holds_host_array(frames):
@@ -117,7 +201,76 @@ class FaceAligner:
             cand = check_rows(rows, len(images), self.device, "the face plan is on %s; there is no CPU fallback")
         else:
             cand = self._check_boxes(boxes, len(images))
-        return self._align(descs or [], cand.detach().contiguous(), boxes is not None, color, matrix, vis_thresh, positions)
+        return self._align(descs or [], cand.detach().contiguous(), boxes is not None, color, matrix, vis_thresh, positions, pose)
+
+    def estimate_pose(self, result):
+        """The head pose of a FaceResult's slots from its position maps -> FacePose (also set as `result.pose`), on the device, in the
+        current stream, no synchronisation.  The same bits as align(..., pose=True) gives."""
+        if self._pose_tables is None:
+            raise ValueError("estimate_pose needs a FaceAligner built with face_ind= and canonical_vertices=")
+        if result.pos is None:
+            raise ValueError("this result was made with positions=False: it holds no position maps (use align(..., pose=True))")
+        self._check_result(result, ("pos", "slots", "xform", "landmarks"))
+        with torch.cuda.device(self.device):
+            result.pose = self._pose(result.pos, True, result.slots, result.xform, result.landmarks)
+        return result.pose
+
+    def _check_result(self, result, names):
+        cap = self.capacity
+        shapes = dict(pos=((cap, RES, RES, 3), torch.float32), slots=((cap,), torch.int32), xform=((cap, 3), torch.float32),
+                      landmarks=((cap, NKPT, 3), torch.float32), P=((cap, 3, 4), torch.float64), box=((cap, 10, 2), torch.int32),
+                      valid=((cap,), torch.int32))
+        for name in names:
+            t = getattr(result.pose if name in ("box", "valid") else result, name)
+            shape, dtype = shapes[name]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError("the result is not one of this aligner's: %s must be a contiguous %s tensor %s on %s (got %s)"
+                                 % (name, str(dtype).replace("torch.", ""), list(shape), self.device,
+                                    "%s %s on %s" % (t.dtype, list(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+
+    def draw(self, frames, result, layout="hwc", color="bgr", matrix="bt601", style=None):
+        """Paint the faces of `result` (a FaceResult of this aligner for these frames) onto `frames`, in place, on the device, in the
+        current stream -> `frames`.  What is drawn is the content of the reference's plot_kpt, plot_vertices and plot_pose_box
+        (demo/face/utils/cv_plot.py) by this project's own rule (csrc/face_draw_arith.h): per face the 60
+        lines between neighbouring landmarks, a disc on each of the 68 landmarks, then the 13 lines of the pose box where the pose is
+        valid; faces in ascending slot order, the last painter wins, opaque, clipped; the dense vertices beneath everything.
+        style: a FaceStyle; the default paints what the live loop pastes (plot_kpt).  pose_box=True on a result without a pose, and
+        vertices=True without position maps or face_ind, raise ValueError.
+        frames: as for draw_results, whose rules for writable frames apply and are checked before anything is launched: expanded or
+        overlapping views, host arrays and the surface colours beyond 8-bit 4:2:0 raise.  The descriptor table is the only upload."""
+        given = frames
+        _check_layout(layout, color, matrix)
+        check_drawable(color, matrix)
+        if _holds_host_array(frames):
+            raise ValueError("draw paints frames on the device (CUDA uint8 tensors): host arrays are not painted, there is no CPU fallback")
+        images, descs = self._io.batch_input(frames, layout, color, matrix)
+        style = FaceStyle() if style is None else style
+        if not isinstance(style, FaceStyle):
+            raise ValueError("style is a FaceStyle (got %s)" % type(style).__name__)
+        if style.pose_box and result.pose is None:
+            raise ValueError("pose_box=True needs a result with a pose (align(..., pose=True) or estimate_pose)")
+        if style.vertices and (result.pos is None or self._pose_tables is None):
+            raise ValueError("vertices=True needs the position maps (positions=True) and an aligner built with face_ind=")
+        self._check_result(result, ["slots", "landmarks"] + (["box", "valid"] if style.pose_box else []) + (["pos"] if style.vertices else []))
+        self._io.check_writable(given, images, color)
+        with torch.cuda.device(self.device):
+            draw_faces(self._io, descs or [], result, self._pose_tables[0] if self._pose_tables is not None else None, color, matrix, style)
+        return given
+
+    def _pose(self, src, from_pos, slots, xform, landmarks):
+        """The two head-pose launches for a source that is the plan's output (from_pos False) or the restored maps."""
+        cap = self.capacity
+        face_ind, canon, stats, scratch = self._pose_tables
+        P = torch.empty((cap, 3, 4), dtype=torch.float64, device=self.device)
+        angles = torch.empty((cap, 3), dtype=torch.float64, device=self.device)
+        scale = torch.empty((cap,), dtype=torch.float64, device=self.device)
+        box = torch.empty((cap, 10, 2), dtype=torch.int32, device=self.device)
+        valid = torch.empty((cap,), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().cp_face_pose_f32(src.data_ptr(), int(from_pos), slots.data_ptr(), xform.data_ptr(), cap, face_ind.data_ptr(),
+                                               int(face_ind.shape[0]), canon.data_ptr(), stats.data_ptr(), landmarks.data_ptr(),
+                                               scratch.data_ptr(), scratch.numel() * 8, P.data_ptr(), angles.data_ptr(), scale.data_ptr(),
+                                               box.data_ptr(), valid.data_ptr(), _lib.stream()), "cp_face_pose_f32")
+        return FacePose(P, angles, scale, box, valid)
 
     def _check_boxes(self, boxes, n_frames):
         if not isinstance(boxes, torch.Tensor):
@@ -134,7 +287,7 @@ class FaceAligner:
             raise _lib.CenterposeHipError("boxes hold %d blocks for %d frames" % (boxes.shape[0], n_frames))
         return boxes
 
-    def _align(self, descs, cand, boxes, color, matrix, vis_thresh, positions):
+    def _align(self, descs, cand, boxes, color, matrix, vis_thresh, positions, pose=False):
         """select + crop + one replay + restore for checked frames and device candidates [N, M, 56 | 5]."""
         yuv = is_yuv(color)
         N, M, cap = len(descs), int(cand.shape[1]), self.capacity
@@ -172,4 +325,5 @@ class FaceAligner:
             _lib.check(L.cp_face_restore_f32(vp(net.data_ptr()), vp(slots.data_ptr()), vp(xform.data_ptr()), cap, vp(self._uv.data_ptr()),
                                              vp(pos.data_ptr()) if positions else None, vp(landmarks.data_ptr()), _lib.stream()),
                        "cp_face_restore_f32")
-        return FaceResult(pos, landmarks, slots, counts, xform)
+            face_pose = self._pose(net, False, slots, xform, landmarks) if pose else None
+        return FaceResult(pos, landmarks, slots, counts, xform, face_pose)

@@ -801,6 +801,71 @@ int cp_face_crop_yuv_frames_host(const void* table_host, int N, const int* coef,
                                  float* out);
 int cp_face_restore_host(const float* net, const int* slots, const float* xform, int cap, const int* uv, float* pos, float* landmarks);
 
+/* ---- head pose of the aligned faces (face.FaceAligner.align(pose=True) / estimate_pose) -----------------------------------------------
+ * What estimate_pose and the projection of plot_pose_box do per face on the host (demo/face/utils/estimate_pose.py:67-99,
+ * cv_plot.py:48-70), for every slot in two launches.  The rule is csrc/face_pose_arith.h: float64, a fixed summation order (chunks of
+ * 2048 vertices, 256 lanes, a binary tree, chunks in ascending order; no atomics), a cyclic Jacobi for the rotation.
+ *   src: DEVICE float32 -- from_pos = 0: the plan's output [cap,3,256,256], restored on the fly (the maps need not exist);
+ *     from_pos = 1: the restored maps [cap,256,256,3].  Both give the same bits.
+ *   slots / xform: as cp_face_select wrote them; a slot is used iff the restore would write it.
+ *   face_ind: DEVICE int [V], cells of the flattened 256 x 256 map, each in 0..65535 (the caller's to check; a cell outside makes the
+ *     slot invalid and is never read); duplicates and any order allowed.  3 <= V <= 65536.
+ *   canon: DEVICE float64 [V,3], the canonical cloud minus its mean; stats: DEVICE float64 [4], that mean and rms_d1.
+ *   landmarks: DEVICE float32 [cap,68,3] (cp_face_restore_f32's): landmarks 0..26 place the box.
+ *   scratch: DEVICE, cp_face_pose_scratch_bytes(cap, V) bytes (0 for arguments out of range); per used slot the chunks' 13 partial
+ *     moments and the pivot vertex; written before it is read, in stream order; an unused slot's part is not touched.
+ *   -> P [cap,3,4] float64 ([s R | t]), angles [cap,3] float64 (matrix2angle's x, y, z), scale [cap] float64, box [cap,10,2] int
+ *     (clamped to -16384..16383, truncated toward zero), valid [cap] int: 1 iff the slot is used, every vertex and moment is finite
+ *     and rms_d0 > 0.  Unused and invalid slots are all zeros.
+ *   Checked before anything is launched (rc 1, cp_last_error): null pointers, cap in 1..256, V in 3..65536, from_pos in {0, 1}, the
+ *   scratch size.  cp_last_kernel(): face_pose_moments_kernel<net|pos>+face_pose_solve_kernel.
+ * cp_face_pose_host: HOST only -- the sequential twin over host arrays, built from the same statements, same checks.  The device
+ *   results equal it bit for bit except the angles (asin / atan2 / cos of two math libraries: within 1e-12 rad). */
+size_t cp_face_pose_scratch_bytes(int cap, int V);
+int cp_face_pose_f32(const float* src, int from_pos, const int* slots, const float* xform, int cap, const int* face_ind, int V,
+                     const double* canon, const double* stats, const float* landmarks, double* scratch, size_t scratch_bytes, double* P,
+                     double* angles, double* scale, int* box, int* valid, void* stream);
+int cp_face_pose_host(const float* src, int from_pos, const int* slots, const float* xform, int cap, const int* face_ind, int V,
+                      const double* canon, const double* stats, const float* landmarks, double* scratch, size_t scratch_bytes, double* P,
+                      double* angles, double* scale, int* box, int* valid);
+
+/* ---- the face overlays on device frames, in place (face.FaceAligner.draw) -------------------------------------------------------------
+ * The content of plot_kpt, plot_vertices and plot_pose_box (demo/face/utils/cv_plot.py) by this library's own rule
+ * (csrc/face_draw_arith.h: the disc and capsule statements of draw_results, k = R^2 + R), not cv2's rasteriser.  Frames and tables
+ * exactly as for cp_draw_rows_frames_u8 / cp_draw_rows_yuv_frames_u8 (same descriptors, same checks; YUV: 8-bit 4:2:0 only).
+ *   slots DEVICE int [cap] (a slot is used iff >= 0; frame n owns slots n * q .. n * q + q - 1, q = cap / N), landmarks DEVICE float32
+ *   [cap,68,3]; box DEVICE int [cap,10,2] and valid DEVICE int [cap] (cp_face_pose_f32's; both NULL without a pose: style.pose_box
+ *   must then be 0); pos DEVICE float32 [cap,256,256,3] and face_ind DEVICE int [V] (NULL unless style.vertices), 1 <= V <= 65536.
+ *   A landmark / vertex sits at rint (half to even) of its x and y clamped to +-16384; a coordinate that is not finite kills its
+ *   primitives.  Per face in paint order: 60 capsules k -> k + 1 (k not in 16, 21, 26, 30, 35, 41, 47, 67), 68 discs, the 13 capsules of
+ *   the pose box where valid == 1.  Faces in ascending slot order, the last painter wins, opaque, clipped; the dense vertices (a disc
+ *   at vertex i * vertex_step of face_ind) lie beneath all faces.  YUV: luma per pixel, chroma from the latest-painted colour among
+ *   the sample's pixels; the style's colours are then (Y, U, V), converted by the caller.
+ *   scratch: DEVICE, 16-byte aligned, cp_face_draw_scratch_bytes(cap) bytes (0 for cap outside 1..256).
+ *   Checked before anything is launched (rc 1): null pointers, 1 <= N <= cap <= 256, radii in 0..3, vertex_step >= 1, pose_box without
+ *   box / valid, vertices without pos / face_ind, V, the scratch, and per frame what draw_results checks.
+ *   cp_last_kernel(): face_draw_kernel<bgr|yuv> (after face_draw_vertices_kernel<bgr|yuv> with style.vertices, and
+ *   face_draw_build_kernel).
+ * cp_face_draw_*_host: HOST only -- sequential painters over host arrays and host frame addresses, same statements, same checks. */
+typedef struct cp_face_style {      /* 48 bytes */
+    int landmarks, vertices, pose_box;                                 /* layers: 0 / 1 */
+    int landmark_radius, line_radius, box_radius, vertex_radius;       /* 0..3 */
+    int vertex_step;                                                   /* >= 1 */
+    unsigned char colors[4][4];     /* landmark, line, vertex, box: bytes 0..2 are stored (channel order B, G, R; or Y, U, V) */
+} cp_face_style;
+int cp_sizeof_face_style(void);
+size_t cp_face_draw_scratch_bytes(int cap);
+int cp_face_draw_frames_u8(const void* table, const void* table_host, int N, const int* slots, int cap, const float* landmarks,
+                           const int* box, const int* valid, const float* pos, const int* face_ind, int V, const void* style,
+                           void* scratch, size_t scratch_bytes, void* stream);
+int cp_face_draw_yuv_frames_u8(const void* table, const void* table_host, int N, const int* slots, int cap, const float* landmarks,
+                               const int* box, const int* valid, const float* pos, const int* face_ind, int V, const void* style,
+                               void* scratch, size_t scratch_bytes, void* stream);
+int cp_face_draw_frames_host(const void* table_host, int N, const int* slots, int cap, const float* landmarks, const int* box,
+                             const int* valid, const float* pos, const int* face_ind, int V, const void* style);
+int cp_face_draw_yuv_frames_host(const void* table_host, int N, const int* slots, int cap, const float* landmarks, const int* box,
+                                 const int* valid, const float* pos, const int* face_ind, int V, const void* style);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
