@@ -43,6 +43,18 @@ def lib():
         faces = [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p]
         _lib.cp_face_draw_frames_host.argtypes = _lib.cp_face_draw_yuv_frames_host.argtypes = faces
         _lib.cp_face_draw_frames_u8.argtypes = _lib.cp_face_draw_yuv_frames_u8.argtypes = [c_void_p] + faces + [c_void_p, c_size_t, c_void_p]
+        # the mesh rasteriser (csrc/face_render.hip)
+        _lib.cp_face_render_scratch_bytes.restype = c_size_t
+        _lib.cp_face_render_scratch_bytes.argtypes = [c_int] * 4
+        render = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                  c_void_p, c_void_p]
+        _lib.cp_face_render_host.argtypes = render
+        _lib.cp_face_render_f32.argtypes = render + [c_void_p]
+        colors = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]
+        _lib.cp_face_vertex_colors_host.argtypes = [c_void_p, c_int] + colors
+        _lib.cp_face_vertex_colors_yuv_host.argtypes = [c_void_p, c_int, c_void_p] + colors
+        _lib.cp_face_vertex_colors_f32.argtypes = [c_void_p, c_void_p, c_int] + colors + [c_void_p]
+        _lib.cp_face_vertex_colors_yuv_f32.argtypes = [c_void_p, c_void_p, c_int, c_void_p] + colors + [c_void_p]
     return _lib
 
 

@@ -7,6 +7,9 @@ out of the frames where they lie on the device (csrc/face_stage.hip), written st
 ``Engine("prnet", ...)`` plan, regressed in one graph replay and restored on the device.  The batch is static (`capacity` crops): a
 data-dependent batch would need the number of selected faces on the host, i.e. a synchronisation.
 
+`FaceRenderer` renders the restored maps where they lie (csrc/face_render.hip): the depth image, the per-pixel triangle index and the
+flat-shaded face of demo/face/utils/render.py, and the vertex colours of PRN.get_colors; it needs the two mesh tables only, no plan.
+
 The crop is a closed-form statement of the reference's pipeline (csrc/face_arith.h): skimage is not available to this project, so it is
 not pinned to a recording of estimate_transform / warp.
 """
@@ -26,6 +29,7 @@ from .reid import _holds_host_array
 FACE_RULE = np.dtype([("vis_thresh", "<f4"), ("expand", "<f4"), ("min_size", "<i4"), ("boxes", "<i4")])
 RES, NKPT, MAX_CAPACITY, MAX_SIZE = 256, 68, 256, 32768
 MIN_VERTICES, MAX_VERTICES = 3, 65536
+MAX_TRIANGLES, MAX_WINDOW, MAX_ORIGIN, MAX_ATTRS = 1 << 22, 4096, 1 << 20, 4
 
 
 def load_prnet_state_dict(path):
@@ -62,18 +66,25 @@ def _load_table(x):
     return np.load(name, allow_pickle=False) if name.endswith(".npy") else np.loadtxt(name)
 
 
-def check_pose_tables(face_ind, canonical_vertices):
-    """The two tables of estimate_pose (get_vertices' face_ind, prnet.py:130-140; canonical_vertices, estimate_pose.py:94), arrays or the
-    paths of the reference's files -> (face_ind int32 [V], the canonical cloud centred in float64 [V, 3], float64 [4]: its mean and
-    rms_d1, estimate_pose.py:73,86), or ValueError.  face_ind: V whole numbers in 0..65535 (cells of the flattened 256 x 256 map),
-    3 <= V <= 65536, duplicates and any order allowed; canonical_vertices: finite [V, 3]."""
-    ind, can = _load_table(face_ind), _load_table(canonical_vertices)
+def check_face_ind(face_ind):
+    """get_vertices' table (prnet.py:130-140), an array or the path of the reference's text file -> int32 [V]: whole numbers in
+    0..65535, 3 <= V <= 65536, or ValueError."""
+    ind = _load_table(face_ind)
     if ind.ndim != 1 or not MIN_VERTICES <= ind.shape[0] <= MAX_VERTICES:
         raise ValueError("face_ind must be one row of %d..%d cells (got shape %s)" % (MIN_VERTICES, MAX_VERTICES, tuple(ind.shape)))
     if ind.dtype.kind not in "iuf" or not np.isfinite(ind.astype(np.float64)).all() or (ind != np.floor(ind)).any():
         raise ValueError("face_ind must hold whole numbers")
     if (ind < 0).any() or (ind >= RES * RES).any():
         raise ValueError("face_ind entries must lie in 0..%d" % (RES * RES - 1))
+    return np.ascontiguousarray(ind.astype(np.int32))
+
+
+def check_pose_tables(face_ind, canonical_vertices):
+    """The two tables of estimate_pose (get_vertices' face_ind, prnet.py:130-140; canonical_vertices, estimate_pose.py:94), arrays or the
+    paths of the reference's files -> (face_ind int32 [V], the canonical cloud centred in float64 [V, 3], float64 [4]: its mean and
+    rms_d1, estimate_pose.py:73,86), or ValueError.  face_ind: V whole numbers in 0..65535 (cells of the flattened 256 x 256 map),
+    3 <= V <= 65536, duplicates and any order allowed; canonical_vertices: finite [V, 3]."""
+    ind, can = check_face_ind(face_ind), _load_table(canonical_vertices)
     if can.dtype.kind not in "iuf" or can.ndim != 2 or can.shape[1] != 3:
         raise ValueError("canonical_vertices must be numbers [V, 3] (got shape %s)" % (tuple(can.shape),))
     if can.shape[0] != ind.shape[0]:
@@ -86,7 +97,36 @@ def check_pose_tables(face_ind, canonical_vertices):
     rms_d1 = float(np.sqrt(np.mean(np.sum(centred * centred, axis=1))))
     if not (np.isfinite(rms_d1) and rms_d1 > 0.0):
         raise ValueError("canonical_vertices must not be one point (rms distance from the mean %r)" % rms_d1)
-    return np.ascontiguousarray(ind.astype(np.int32)), centred, np.asarray([mean[0], mean[1], mean[2], rms_d1], np.float64)
+    return ind, centred, np.asarray([mean[0], mean[1], mean[2], rms_d1], np.float64)
+
+
+def check_triangles(triangles, V):
+    """A mesh over V vertices, an array [T, 3] or the path of a text file of one (the reference's triangles.txt) -> int32 [T, 3]: whole
+    numbers in 0..V-1, 1 <= T <= 2^22, or ValueError.  The kernels do not check the table again."""
+    tri = _load_table(triangles)
+    if tri.ndim != 2 or tri.shape[1] != 3 or not 1 <= tri.shape[0] <= MAX_TRIANGLES:
+        raise ValueError("triangles must be [T, 3] with T in 1..%d (got shape %s)" % (MAX_TRIANGLES, tuple(tri.shape)))
+    if tri.dtype.kind not in "iuf" or not np.isfinite(tri.astype(np.float64)).all() or (tri != np.floor(tri)).any():
+        raise ValueError("triangles must hold whole numbers")
+    if (tri < 0).any() or (tri >= V).any():
+        raise ValueError("triangles must name vertices 0..%d" % (V - 1))
+    return np.ascontiguousarray(tri.astype(np.int32))
+
+
+def grid_triangles(face_ind):
+    """A mesh for a caller without the reference's triangles.txt -> int32 [T, 3]: the two triangles (tl, bl, tr) and (bl, br, tr) of
+    every 2 x 2 block of map cells whose four corners are in `face_ind`, blocks in row-major order, as indices into face_ind (the first
+    entry of a cell that is listed twice).  ValueError when no block is complete."""
+    ind = check_face_ind(face_ind)
+    where = np.full(RES * RES, -1, np.int64)
+    where[ind[::-1]] = np.arange(len(ind) - 1, -1, -1)
+    grid = where.reshape(RES, RES)
+    tl, bl, tr, br = grid[:-1, :-1], grid[1:, :-1], grid[:-1, 1:], grid[1:, 1:]
+    full = (tl >= 0) & (bl >= 0) & (tr >= 0) & (br >= 0)
+    if not full.any():
+        raise ValueError("face_ind holds no 2 x 2 block of map cells: no triangle")
+    tl, bl, tr, br = tl[full], bl[full], tr[full], br[full]
+    return np.ascontiguousarray(np.stack([np.stack([tl, bl, tr], 1), np.stack([bl, br, tr], 1)], 1).reshape(-1, 3).astype(np.int32))
 
 
 class FacePose:
@@ -125,6 +165,131 @@ class FaceResult:
             raise ValueError("this result was made with positions=False: it holds the landmarks only")
         idx = torch.as_tensor(np.asarray(face_ind), dtype=torch.long, device=self.pos.device)
         return self.pos.reshape(self.pos.shape[0], RES * RES, 3)[:, idx]
+
+
+class FaceRender:
+    """What one `render` call returns, on the device, ready in the current stream's order:
+    tri [capacity, h, w] int32 -- the index of the triangle seen at every pixel of the slot's window, -1 for none (get_triangle_buffer);
+    image [capacity, h, w, C] float32 -- the mean of that triangle's three vertex attributes, 0 where nothing covers (render_texture;
+    with attrs=None the depth image of get_depth_image, C = 1).  Unused slots are all -1 / 0."""
+    __slots__ = ("tri", "image")
+
+    def __init__(self, tri, image):
+        self.tri, self.image = tri, image
+
+
+class FaceRenderer:
+    """The z-buffer rasteriser over the position maps of `capacity` slots and their vertex colours (csrc/face_render.hip; DESIGN.md
+    section 4.17).  It needs no PRNet plan: only the two tables.
+    face_ind: get_vertices' table (`check_face_ind`); triangles: [T, 3] whole numbers in 0..V-1 or the path of a text file of them
+    (`check_triangles`; `grid_triangles(face_ind)` makes a mesh).  The product ships no reference data."""
+
+    def __init__(self, face_ind, triangles, capacity, device="cuda"):
+        capacity = int(capacity)
+        if not 1 <= capacity <= MAX_CAPACITY:
+            raise ValueError("capacity must lie in 1..%d (got %d)" % (MAX_CAPACITY, capacity))
+        ind = check_face_ind(face_ind)
+        tri = check_triangles(triangles, len(ind))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("the renderer runs on the GPU (got device %s): there is no CPU fallback" % device)
+        self.device = device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.capacity, self.face_ind, self.triangles = capacity, ind, tri
+        self._io = FrameIO(self.device)
+        with torch.cuda.device(self.device):
+            self._ind = torch.from_numpy(ind).to(self.device)
+            self._tri = torch.from_numpy(tri).to(self.device)
+            self._zero_origin = torch.zeros((capacity, 2), dtype=torch.int32, device=self.device)
+
+    def _check(self, t, name, shape, dtype):
+        if isinstance(t, np.ndarray):
+            raise ValueError("%s is a host array: the renderer reads CUDA tensors, there is no CPU fallback" % name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor %s on %s (got %s)"
+                             % (name, str(dtype).replace("torch.", ""), list(shape), self.device,
+                                "%s %s on %s" % (t.dtype, list(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+
+    def _maps(self, result_or_pos, slots):
+        """-> (pos, slots) of a FaceResult or of a pos tensor with its slots, checked."""
+        if isinstance(result_or_pos, FaceResult):
+            if slots is not None:
+                raise ValueError("slots= goes with a pos tensor: a FaceResult brings its own")
+            if result_or_pos.pos is None:
+                raise ValueError("this result was made with positions=False: it holds no position maps")
+            pos, slots = result_or_pos.pos, result_or_pos.slots
+        else:
+            pos = result_or_pos
+            if slots is None:
+                raise ValueError("a pos tensor needs slots= (int32 [capacity], -1 for an unused slot)")
+        self._check(pos, "pos", (self.capacity, RES, RES, 3), torch.float32)
+        self._check(slots, "slots", (self.capacity,), torch.int32)
+        return pos, slots
+
+    def render(self, result_or_pos, slots=None, size=None, origin=None, attrs=None):
+        """Rasterise every slot's mesh into its window -> FaceRender(tri, image), on the device, in the current stream, no
+        synchronisation and no upload.
+        result_or_pos: a FaceResult with position maps, or a CUDA float32 tensor [capacity, 256, 256, 3] with slots= (CUDA int32
+        [capacity], a slot is used iff >= 0).
+        size: (h, w) of every window, 1..4096 each, capacity * h * w * 8 < 2^31.
+        origin: None (every window starts at frame pixel (0, 0)) or CUDA int32 [capacity, 2] = (x0, y0): image pixel (r, c) of slot s is
+        frame pixel (x0 + c, y0 + r).  A slot whose origin lies outside +-2^20 is rendered like an unused one.
+        attrs: None (the vertices' z: the depth image) or CUDA float32 [capacity, V, C], 1 <= C <= 4, e.g. `vertex_colors`.
+        The rule is csrc/face_render_arith.h: a triangle's box is clamped to the window, so the result is the reference's render of any
+        frame that contains the window, cropped to it."""
+        pos, slots = self._maps(result_or_pos, slots)
+        if (not isinstance(size, (tuple, list)) or len(size) != 2
+                or not all(isinstance(v, (int, np.integer)) and 1 <= int(v) <= MAX_WINDOW for v in size)):
+            raise ValueError("size must be (h, w) with both in 1..%d (got %r)" % (MAX_WINDOW, size))
+        h, w = int(size[0]), int(size[1])
+        cap, V = self.capacity, len(self.face_ind)
+        if cap * h * w * 8 >= 1 << 31:
+            raise ValueError("%d windows of %d x %d: the key buffer reaches 2^31 bytes" % (cap, h, w))
+        if origin is None:
+            origin = self._zero_origin
+        else:
+            self._check(origin, "origin", (cap, 2), torch.int32)
+        C = 1
+        if attrs is not None:
+            if isinstance(attrs, torch.Tensor) and attrs.dim() == 3 and 1 <= attrs.shape[2] <= MAX_ATTRS:
+                C = int(attrs.shape[2])
+            self._check(attrs, "attrs", (cap, V, C), torch.float32)
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            nbytes = int(L.cp_face_render_scratch_bytes(cap, h, w, int(self._tri.shape[0])))
+            scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=self.device)
+            tri = torch.empty((cap, h, w), dtype=torch.int32, device=self.device)
+            image = torch.empty((cap, h, w, C), dtype=torch.float32, device=self.device)
+            _lib.check(L.cp_face_render_f32(pos.data_ptr(), slots.data_ptr(), cap, self._ind.data_ptr(), V, self._tri.data_ptr(),
+                                            int(self._tri.shape[0]), origin.data_ptr(), h, w, None if attrs is None else attrs.data_ptr(), C,
+                                            scratch.data_ptr(), nbytes, tri.data_ptr(), image.data_ptr(), _lib.stream()), "cp_face_render_f32")
+        return FaceRender(tri, image)
+
+    def vertex_colors(self, frames, result, slots=None, layout="hwc", color="bgr", matrix="bt601"):
+        """The colour of every vertex where it lies in its frame (PRN.get_colors, prnet.py:155-168) -> float32 [capacity, V, 3] =
+        (B, G, R) in 0..255, on the device, in the current stream; the descriptor table is the only upload.  Per vertex x is clamped to
+        [0, W - 1], y to [0, H - 1], both rounded half to even; zeros for a coordinate that is not finite and for unused slots.
+        frames: as for FaceAligner.align (any layout, BGR / RGB, every YUV colour and matrix); they are only read.  Frame n owns the
+        slots n * q .. n * q + q - 1, q = capacity // N, as align fills them.  result: as for `render` (a pos tensor with slots=)."""
+        pos, slots = self._maps(result, slots)
+        if _holds_host_array(frames):
+            raise ValueError("vertex_colors reads device frames (CUDA uint8 tensors): host arrays are not read, there is no CPU fallback")
+        images, descs = self._io.batch_input(frames, layout, color, matrix)
+        N, cap, V = len(descs or []), self.capacity, len(self.face_ind)
+        if not 1 <= N <= cap:
+            raise ValueError("%d frames for a capacity of %d slots" % (N, cap))
+        yuv = is_yuv(color)
+        table = identity_table(descs, yuv)
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            colors = torch.empty((cap, V, 3), dtype=torch.float32, device=self.device)
+            table_dev, = self._io.upload_table([table])
+            tail = (pos.data_ptr(), slots.data_ptr(), cap, self._ind.data_ptr(), V, colors.data_ptr(), _lib.stream())
+            if yuv:
+                coef = (ctypes.c_int * 6)(*yuv_coef(matrix))
+                _lib.check(L.cp_face_vertex_colors_yuv_f32(table_dev.data_ptr(), table.ctypes.data, N, coef, *tail), "cp_face_vertex_colors_yuv_f32")
+            else:
+                _lib.check(L.cp_face_vertex_colors_f32(table_dev.data_ptr(), table.ctypes.data, N, *tail), "cp_face_vertex_colors_f32")
+        return colors
 
 
 class FaceAligner:
@@ -177,6 +342,12 @@ class FaceAligner:
     def has_pose_tables(self):
         """True iff the aligner was built with face_ind and canonical_vertices: pose=True and estimate_pose are available."""
         return self._pose_tables is not None
+
+    def renderer(self, triangles):
+        """A FaceRenderer over this aligner's face_ind and capacity, on its device.  triangles: as for FaceRenderer."""
+        if self.face_ind is None:
+            raise ValueError("renderer needs a FaceAligner built with face_ind= (and canonical_vertices=)")
+        return FaceRenderer(self.face_ind, triangles, self.capacity, device=self.device)
 
     def align(self, frames, rows=None, boxes=None, layout="hwc", color="bgr", matrix="bt601", vis_thresh=0.3, positions=True, pose=False):
         """Position maps and landmarks of the faces of `frames` -> FaceResult, on the device, in the current stream, no

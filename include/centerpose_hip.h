@@ -866,6 +866,48 @@ int cp_face_draw_frames_host(const void* table_host, int N, const int* slots, in
 int cp_face_draw_yuv_frames_host(const void* table_host, int N, const int* slots, int cap, const float* landmarks, const int* box,
                                  const int* valid, const float* pos, const int* face_ind, int V, const void* style);
 
+/* ---- the aligned faces rendered: z-buffer mesh rasteriser and vertex colours (face.FaceRenderer) -----------------------------------------
+ * What render_texture, get_triangle_buffer and get_depth_image (demo/face/utils/render.py:85-120, 239-287; render_app.py:35-40) compute
+ * per face in three nested Python loops, for every slot in three launches.  The rule is csrc/face_render_arith.h: float64 on the
+ * float32 inputs; per triangle i the depth d = (float)(((z0 + z1) + z2) / 3.0) + 0.0f, the box clamped to the slot's WINDOW (the
+ * reference clamps to the frame: the result is its render of any frame that contains the window, cropped to it), isPointInTri with
+ * the reference's statements (a degenerate triangle covers its whole box); triangles with a coordinate that is not finite or with
+ * !(d > -999999) are skipped.  The winner of a pixel is the maximum of the 64-bit key ordered(d) << 32 | (0xFFFFFFFF - i): the largest
+ * depth, among equal depths the smallest index, whatever the arrival order -- the output is the same bits from run to run.
+ *   pos: DEVICE float32 [cap,256,256,3] (cp_face_restore_f32's); slots: DEVICE int [cap], a slot is used iff >= 0.
+ *   face_ind: DEVICE int [V] in 0..65535, 3 <= V <= 65536; tri: DEVICE int [T,3] in 0..V-1, 1 <= T <= 2^22.  Both tables are the
+ *     caller's to check when it uploads them; they are not re-checked per launch.
+ *   origin: DEVICE int [cap,2] = (x0, y0): image pixel (r, c) of slot s is frame pixel (x0[s] + c, y0[s] + r); a slot whose origin lies
+ *     outside +-2^20 is written like an unused one.  h, w in 1..4096 with cap * h * w * 8 < 2^31.
+ *   attrs: DEVICE float32 [cap,V,C], 1 <= C <= 4, or NULL: the vertices' z (C = 1; the depth image).
+ *   scratch: DEVICE, 8-byte aligned, cp_face_render_scratch_bytes(cap, h, w, T) bytes (0 for arguments out of range): the keys
+ *     [cap,h,w], cleared by the call itself.
+ *   -> out_tri int [cap,h,w] (-1: no triangle), out_image float32 [cap,h,w,C]: (float)(((a0 + a1) + a2) / 3.0) of the winner's three
+ *     vertex attributes, 0 where nothing covers.  Unused slots: all -1 / 0.
+ *   Checked before anything is launched (rc 1, cp_last_error): null pointers, the ranges above, NULL attrs with C != 1, the scratch.
+ *   cp_last_kernel(): face_render_clear_kernel+face_render_raster_kernel+face_render_resolve_kernel.
+ * cp_face_vertex_colors_f32 / _yuv_f32: PRN.get_colors (demo/face/prnet.py:155-168) for every slot -- per vertex x clamped to
+ *   [0, W-1], y to [0, H-1], rounded half to even, the frame's (B, G, R) there as float32 0..255 -> colors [cap,V,3]; zeros for a vertex
+ *   with a coordinate that is not finite and for unused slots.  Frames and tables exactly as for cp_face_crop_frames_f32 /
+ *   cp_face_crop_yuv_frames_f32 (same descriptors, same checks, every format word); frame n owns slots n * q .. n * q + q - 1,
+ *   q = cap / N.  The frames are only read.  cp_last_kernel(): face_vertex_colors_kernel<bgr|yuv|surfaces>.
+ * cp_face_*_host: HOST only -- the sequential twins over host arrays, built from the same statements, same checks; the render twin also
+ *   checks face_ind and tri.  The device results equal them bit for bit. */
+size_t cp_face_render_scratch_bytes(int cap, int h, int w, int T);
+int cp_face_render_f32(const float* pos, const int* slots, int cap, const int* face_ind, int V, const int* tri, int T, const int* origin,
+                       int h, int w, const float* attrs, int C, void* scratch, size_t scratch_bytes, int* out_tri, float* out_image,
+                       void* stream);
+int cp_face_render_host(const float* pos, const int* slots, int cap, const int* face_ind, int V, const int* tri, int T, const int* origin,
+                        int h, int w, const float* attrs, int C, void* scratch, size_t scratch_bytes, int* out_tri, float* out_image);
+int cp_face_vertex_colors_f32(const void* table, const void* table_host, int N, const float* pos, const int* slots, int cap,
+                              const int* face_ind, int V, float* colors, void* stream);
+int cp_face_vertex_colors_yuv_f32(const void* table, const void* table_host, int N, const int* coef, const float* pos, const int* slots,
+                                  int cap, const int* face_ind, int V, float* colors, void* stream);
+int cp_face_vertex_colors_host(const void* table_host, int N, const float* pos, const int* slots, int cap, const int* face_ind, int V,
+                               float* colors);
+int cp_face_vertex_colors_yuv_host(const void* table_host, int N, const int* coef, const float* pos, const int* slots, int cap,
+                                   const int* face_ind, int V, float* colors);
+
 /* ---- host: soft-NMS of merged results --------------------------------------------------------
  * Replaces soft_nms_39 (lib/external/nms.pyx:172-275; called from multi_pose.py:76-77).
  * boxes: HOST float32 [N,56], modified in place with the reference's quirks; keep: HOST int[N] or NULL. */
